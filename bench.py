@@ -21,7 +21,14 @@ is the model's own output, the CTC cost (:37-39,178; `--loss sum`: the linear st
 every rank holds a replica; gradients are summed with bucketed RCCL all-reduces launched while the backward is still running (qcnn_amd/dp.py), 1/N folded into
 the fused Adam kernel.
 
-Prints ONE JSON line on rank 0.  `value` = whole-job samples/s of that step.  At N = 1 the line also carries
+Prints ONE JSON line on rank 0.  `value` = whole-job samples/s of that step, `ms_per_step` = wall time of one timed step.
+A plain run does only that: set-up, warm-up, the timed steps and the line.  `--dump-outputs DIR` then also writes what the last
+timed step computed -- what a caller of the step receives: the loss and the updated parameters (a layer workload: also its
+output and input gradient; Adam's moments are the optimizer's own state) -- as DIR/<name>.npy in float32, arrays above 2 M
+elements as a fixed seeded sample, so that two builds can be compared output for output on identical inputs.  The step's float
+atomics (backward-weight split sums) reorder additions from run to run, and Adam turns that rounding in near-zero gradients
+into lr-sized updates: default workload, relative L2 difference of two runs 5e-6 (loss) / 9e-5 (parameters) after 3 steps,
+1e-4 / 9e-4 after 57; QK_DETERMINISTIC makes them bit-identical at 10x the step time.  Everything else is measured only under `--full`; at N = 1 that line also carries
   roofline       the kernel that takes the largest share of the step (one of the Hamilton GEMM kernels of the
                  64 -> 64 body convolution, M = 716 800, N = 256, K = 3840): 2MNK / its MEAN launch duration measured
                  live with HIP events on the launch stream, against the 2.5 PF dense bf16 MFMA peak; traffic = HBM bytes
@@ -30,6 +37,7 @@ Prints ONE JSON line on rank 0.  `value` = whole-job samples/s of that step.  At
   layer_kernels  the other two conv shapes of the model (32 -> 32, 32 -> 64)
   cfg2_layer     BASELINE configs[1]: one QuaternionConv1D(64, 3, 'same', relu) on x (64, 200, 160) fp32, step + kernels
   cpu_baseline   the reference's CPU op sequence for the same model (oracle/ref_model.py on torch-CPU), bounded sample
+and, at every N, `gpu_telemetry` (power / clock during the timed steps) and the exposed-collective A/B of the `dp` block.
 `--workload` selects any single-layer workload instead (then `roofline` is that layer's dominant kernel).
 """
 import argparse
@@ -170,6 +178,7 @@ class ModelTrainStep(object):
         else:
             pred = self.model(self.x)
             loss = self.F.weighted_sum(pred, self.target)            # sum(pred * target): one launch each way
+        self.last_loss = loss.detach()                  # (--dump-outputs; no launch)
         loss.backward()                                 # gradients accumulate into the zeroed flat buffer; the
         self.reducer.finish()                           # buckets go out while the backward is still running
         # the step number is a DEVICE counter once capture() has run (qk_adam_step_dev): no launch argument of the step
@@ -200,6 +209,9 @@ class ModelTrainStep(object):
             self._step_body()
         torch.cuda.synchronize(dev)
         self.graph = g
+
+    def outputs(self):
+        return {'loss': self.last_loss, 'params': self.flat.param}
 
 
 class StackTrainStep(object):
@@ -243,12 +255,17 @@ class StackTrainStep(object):
         F = self.F
         h = F.quaternion_conv(self.x, self.ws[0], self.bs[0], **self.kws[0])
         y = F.quaternion_conv_chain(h, [(self.ws[i], self.bs[i], self.kws[i]) for i in range(1, len(self.ws))])
-        (y.float() * self.target).sum().backward()
+        loss = (y.float() * self.target).sum()
+        self.last_loss = loss.detach()                  # (--dump-outputs; no launch)
+        loss.backward()
         self.reducer.finish()
         F.adam_step(self.flat.param, self.flat.grad, self.m, self.v, self.t, lr=5e-4, grad_scale=1.0 / self.world, zero_grad=True)
 
     def capture(self):
         raise RuntimeError('stack workloads run eagerly')
+
+    def outputs(self):
+        return {'loss': self.last_loss, 'params': self.flat.param}
 
 
 class LayerTrainStep(object):
@@ -379,6 +396,28 @@ class LayerTrainStep(object):
         self.g_b.replay()                   # bwd-data runs while the gradients travel over xGMI
         work.wait()
         self.g_c.replay()
+
+    def outputs(self):
+        return {'y': self.y, 'dx': self.dx, 'params': self.flat.param}
+
+
+DUMP_MAX_ELEMENTS = 1 << 21      # per array (8 MB in float32): a step dumps at most three arrays, < 64 MB in all
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, in its own shape; one with more than DUMP_MAX_ELEMENTS
+    elements as a fixed sample of its flattened values (sorted indices from a fixed seed), the same elements in every run.
+    Raises ValueError, before writing anything, when the files would exceed 64 MB in all."""
+    total = sum(4 * min(t.numel(), DUMP_MAX_ELEMENTS) for t in arrays.values())
+    if total > 64 << 20:
+        raise ValueError('--dump-outputs: %d bytes of arrays, more than 64 MB' % total)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.RandomState(0).randint(0, t.numel(), DUMP_MAX_ELEMENTS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.float().cpu().numpy())
 
 
 def pmc_traffic(workload, kernel):
@@ -753,10 +792,10 @@ def timed_steps(job, steps, warmup, pre, barrier, world, dev, dist, per_rank=Non
     return elapsed
 
 
-def dp_proof(job, steps, ms_per_step, per_rank, barrier, world, dev, dist):
+def dp_proof(job, steps, ms_per_step, per_rank, barrier, world, dev, dist, ab=True):
     """What shows that `world` RCCL ranks really ran the step together (N > 1, or a forced one-rank group): the rank
-    count as an all-reduce of ones sees it, every rank's own step time, the gradient buckets, and the EXPOSED cost of
-    the collectives = this step's time minus the same step with the all-reduces switched off (hooks still count, nothing
+    count as an all-reduce of ones sees it, every rank's own step time, the gradient buckets, and (`ab`, --full) the EXPOSED
+    cost of the collectives = this step's time minus the same step with the all-reduces switched off (hooks still count, nothing
     is sent: BucketedAllReduce.enabled = False; replicas drift apart during those steps, which no longer matters)."""
     ones = torch.ones(1, device=dev)
     dist.all_reduce(ones)
@@ -768,6 +807,7 @@ def dp_proof(job, steps, ms_per_step, per_rank, barrier, world, dev, dist):
         nb = red.bucket_bytes()
         out['allreduce'] = {'buckets': len(nb), 'bucket_bytes': nb, 'bytes_per_step': int(sum(nb)), 'dtype': 'fp32',
                             'launch': 'per bucket, from the backward (autograd hook / kernel-side notification)'}
+    if red is not None and ab:
         # interleaved A/B behind the timed region (on, off, on, off segments of k steps each): the same clock / thermal
         # state for both, unlike "the timed region vs a later segment" (which read 0.3 - 0.5 ms "exposed" for ONE bucket on
         # ONE rank, where nothing is sent at all)
@@ -795,6 +835,12 @@ def main():
     ap.add_argument('--steps', type=int, default=None, help='timed steps (default: 100 for the QCNN, 300 for a layer)')
     ap.add_argument('--warmup', type=int, default=None, help='untimed warm-up steps (default: 10 / 30)')
     ap.add_argument('--workload', default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (float32, < 64 MB in all)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: power / clock telemetry, in-step and stand-alone kernel timing, '
+                         'roofline, the other workloads, the exposed-collective A/B, the CPU baseline (the --no-* options below '
+                         'leave parts of it out)')
     ap.add_argument('--cpu-seconds', type=float, default=24.0)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true')
@@ -870,13 +916,15 @@ def main():
     # the code objects, size the workspaces and settle the allocator.  Reported in the JSON; never timed.
     pre = 2 if is_model else 8
     per_rank = []
-    tele, tele_win = (GpuTelemetry(dev) if rank == 0 else None), {}
+    tele, tele_win = (GpuTelemetry(dev) if rank == 0 and args.full else None), {}
     if tele is not None:
         tele.start()
     elapsed = timed_steps(job, steps, warmup, pre, barrier, world, dev, dist, per_rank, tele_win)
     tele_out = tele.summary(*tele_win['window']) if tele is not None and 'window' in tele_win else None
     ms_per_step = 1e3 * elapsed / steps
     samples_per_s = world * cfg['batch'] * steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job.outputs(), args.dump_outputs)      # before anything below runs more steps on the job
 
     out = {
         'metric': 'quaternion-conv samples/sec (fwd+bwd+Adam of %s)' % ('the config-5 stack, per-GPU batch %d' % cfg['batch'] if is_stack else 'the full TIMIT QCNN, per-GPU batch %d' % cfg['batch'] if is_model else 'one QuaternionConv layer'),
@@ -897,10 +945,11 @@ def main():
                    'optimizer': 'adam(5e-4)' + (' + l2 term folded into the update' if cfg.get('l2') else ''),
                    'launch': 'hipgraph' if use_graph else 'eager'},
     }
-    out['gpu_telemetry'] = tele_out          # socket W / shader MHz during the timed steps (None where sysfs does not show them)
+    if args.full:
+        out['gpu_telemetry'] = tele_out      # socket W / shader MHz during the timed steps (None where sysfs does not show them)
     if dist.is_initialized():
         try:
-            proof = dp_proof(job, steps, ms_per_step, per_rank, barrier, world, dev, dist)
+            proof = dp_proof(job, steps, ms_per_step, per_rank, barrier, world, dev, dist, ab=args.full)
             out['config']['rccl_ranks'] = proof.pop('rccl_ranks')
             out['dp'] = proof
         except Exception as e:
@@ -909,7 +958,7 @@ def main():
         out['config']['rccl_ranks'] = None
     peak = PEAK_TFLOPS[cfg['dtype']]
     stream = torch.cuda.current_stream(dev)
-    timing = rank == 0 and world == 1 and not args.no_kernel_timing and not is_stack
+    timing = args.full and rank == 0 and world == 1 and not args.no_kernel_timing and not is_stack
 
     if rank == 0 and is_model:
         tf = 3 * job.flops_per_kernel / (ms_per_step * 1e-3) / 1e12
@@ -924,7 +973,7 @@ def main():
             out['j_per_tflop'] = out['energy_j_per_step'] / (3 * job.flops_per_kernel / 1e12)
             out['energy_note'] = ('socket energy of the %d timed steps (rank 0) / steps; j_per_tflop = that / the step\'s algorithmic TFLOP '
                                   '(%.2f); %s' % (steps, 3 * job.flops_per_kernel / 1e12, tele_out.get('energy_method')))
-    if rank == 0 and world == 1 and is_model and not args.no_kernel_timing:
+    if args.full and rank == 0 and world == 1 and is_model and not args.no_kernel_timing:
         try:
             out['in_step_kernels'] = in_step_kernel_times(job, dev, peak)
         except Exception as e:
@@ -1119,7 +1168,7 @@ def main():
         out['step_tflops'] = 3 * job.flops_per_kernel / (ms_per_step * 1e-3) / 1e12
     if world > 1:
         dist.barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not is_stack:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not is_stack:
         out['cpu_baseline'] = cpu_baseline(cfg, args.cpu_seconds, args.loss)
     if rank == 0:
         print(json.dumps(out))

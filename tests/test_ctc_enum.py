@@ -93,8 +93,11 @@ def test_fused_ctc_kernels_equal_the_enumerated_cost_and_gradient(case, form, dt
     up = 0.5 + np.random.RandomState(1).rand(y.shape[0])
     g_want = ctc_enum.ctc_grad_fd(y_seen, labels, il, ll, upstream=up)
     finite = np.isfinite(want[:, 0])
-    if dtype == torch.float16 and np.nanmax(np.abs(g_want[finite])) > 6e4:
-        pytest.skip('d cost / d y_pred = (...) / (y_pred + 1e-7) leaves float16\'s range at near-zero posteriors (no loss scaling can help a STORED gradient)')
+    # d cost / d y_pred = (...) / (y_pred + 1e-7) can leave float16's range at near-zero posteriors (no loss scaling can help a
+    # STORED gradient): such entries are checked to saturate with the right sign, the others as usual
+    big = np.zeros_like(g_want, dtype=bool)
+    if dtype == torch.float16:
+        big[finite] = np.abs(g_want[finite]) > 6e4
     with _lib.debug_flags(_lib.QK_DBG_CTC_TWO_SWEEPS if form == 'two_sweeps' else 0):
         p = yd.to(dev).requires_grad_(True)
         assert Fq.ctc_supported(p, torch.tensor(labels))
@@ -107,9 +110,13 @@ def test_fused_ctc_kernels_equal_the_enumerated_cost_and_gradient(case, form, dt
     err_c = np.abs(got[finite] - want[finite]).max() / max(np.abs(want[finite]).max(), 1e-30)
     assert err_c <= 2e-5, err_c
     g = p.grad.double().cpu().numpy()
-    err_g = np.abs(g[finite] - g_want[finite]).max() / np.abs(g_want[finite]).max()
     tol = {torch.float32: 5e-4, torch.bfloat16: 1e-2, torch.float16: 2e-3}[dtype]
+    ok = finite[:, None, None] & ~big
+    err_g = np.abs(g[ok] - g_want[ok]).max() / np.abs(g_want[ok]).max()
     assert err_g <= tol, err_g
+    if big.any():
+        assert np.all(np.sign(g[big]) == np.sign(g_want[big])), g[big]
+        assert np.all(np.abs(g[big]) >= (1 - tol) * np.minimum(np.abs(g_want[big]), 65504.0)), g[big]
     assert np.all(g[~finite] == 0.0)                                                       # infeasible samples send nothing back
     for b in range(y.shape[0]):
         assert np.all(g[b, int(il[b]):] == 0.0)

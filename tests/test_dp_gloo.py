@@ -108,7 +108,7 @@ def test_bench_step_through_one_rank_rccl_group():
     env = dict(os.environ, QK_DP_FORCE_COLLECTIVES='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.join(root, 'bench.py'),
-           '--gpus', '1', '--steps', '10', '--warmup', '2', '--no-cpu-baseline', '--no-kernel-timing']
+           '--gpus', '1', '--steps', '10', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-kernel-timing']
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1]
@@ -594,7 +594,7 @@ def test_plain_bench_gpus_n_starts_its_ranks_and_prints_one_line(world, workload
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
     env.update(QK_DP_SHARE_DEVICE='1', QK_DP_BACKEND='gloo')
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '3', '--warmup', '1',
-           '--no-cpu-baseline', '--no-extras', '--no-kernel-timing'] + (['--workload', workload] if workload else [])
+           '--full', '--no-cpu-baseline', '--no-extras', '--no-kernel-timing'] + (['--workload', workload] if workload else [])
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=root)
     if out.returncode != 0 and world > 2 and 'Connection closed by peer' in out.stderr:
         # Eight processes time-slicing ONE GPU over gloo's TCP pairs: seen once in round 5 to lose a rank during start-up

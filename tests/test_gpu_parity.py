@@ -39,6 +39,17 @@ def _rel_err(got, want):
     return float(np.abs(got - want).max()) / max(float(np.abs(want).max()), 1e-30)
 
 
+def _run_native(F, rec_x, rec_w, rec_b, rec_dy, rank, kw, dtype):
+    """The native layout on a case: a channels_last convolution goes in its channels_first form (the same numbers, channel
+    axis moved) through internal_layout='native', and y / dx come back channels_last; a dense layer has no layout."""
+    if rank == 0 or kw.get('data_format', 'channels_last') == 'channels_first':
+        return _run_layer(F, rec_x, rec_w, rec_b, rec_dy, rank, kw, dtype, 'native')
+    got = _run_layer(F, np.moveaxis(rec_x, -1, 1), rec_w, rec_b, np.moveaxis(rec_dy, -1, 1), rank,
+                     dict(kw, data_format='channels_first'), dtype, 'native')
+    got['y'], got['dx'] = np.moveaxis(got['y'], 1, -1), np.moveaxis(got['dx'], 1, -1)
+    return got
+
+
 def _run_layer(F, rec_x, rec_w, rec_b, rec_dy, rank, kw, dtype, internal_layout='channels_last'):
     dev = _dev()
     x = torch.tensor(rec_x, device=dev).to(dtype).requires_grad_(True)
@@ -66,10 +77,8 @@ def test_fp32_matches_reference_golden(path, layout):
     import qcnn_amd
     rec, cfg = load_golden(path)
     rank, kw = layer_kwargs(cfg)
-    if layout == 'native' and kw.get('data_format', 'channels_last') != 'channels_first':
-        pytest.skip('native == channels_last for this case')
-    got = _run_layer(qcnn_amd.functional, rec['x'], rec['kernel'], rec.get('bias'), rec['dy'], rank, kw,
-                     torch.float32, layout)
+    run = _run_native if layout == 'native' else _run_layer
+    got = run(qcnn_amd.functional, rec['x'], rec['kernel'], rec.get('bias'), rec['dy'], rank, kw, torch.float32)
     for k, v in got.items():
         err = _rel_err(v, rec[k])
         assert err <= 1e-4, '%s: rel err %.3g' % (k, err)
@@ -1690,10 +1699,9 @@ def test_random_layer_configurations_match_oracle(case, dtype, layout):
     tests, so breadth over its argument space is ours to supply."""
     import qcnn_amd
     _, rank, xs, ws, kw, bias = case
-    if layout == 'native' and (rank == 0 or kw.get('data_format') != 'channels_first'):
-        pytest.skip('native == channels_last for this configuration')
     x, w, b, dy, want = _oracle_case(rank, xs, ws, kw, seed=77, dtype=dtype, use_bias=bias)
-    got = _run_layer(qcnn_amd.functional, x, w, b, dy, rank, dict(kw), dtype, internal_layout=layout)
+    run = _run_native if layout == 'native' else _run_layer
+    got = run(qcnn_amd.functional, x, w, b, dy, rank, dict(kw), dtype)
     tol16, tol32 = (1e-4, 1e-4) if dtype == torch.float32 else (1e-2, 3e-3)
     for k, v in got.items():
         err = _rel_err(v, want[k])

@@ -574,7 +574,7 @@ def test_bench_prints_one_contract_line():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline',
                           '--no-extras', '--no-standalone'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -593,6 +593,53 @@ def test_bench_prints_one_contract_line():
     r = d['roofline']
     assert r['bound'] == 'mfma' and r['peak'] == 2500.0 and abs(r['frac'] - r['achieved'] / r['peak']) < 1e-9
     assert abs(r['achieved'] - r['flops_per_launch'] / (r['avg_launch_ms'] * 1e-3) / 1e12) <= 1e-6 * r['achieved']
+
+
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample_of_large_arrays(tmp_path):
+    """bench.dump_outputs: every array as <name>.npy in float32 in its own shape; an array above DUMP_MAX_ELEMENTS as the same
+    seeded sample of its flattened values in every run."""
+    import bench
+    big = torch.randn(3, bench.DUMP_MAX_ELEMENTS, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16)
+    arrays = {'loss': torch.tensor(2.5), 'params': torch.arange(10.0).reshape(2, 5), 'big': big}
+    for d in ('a', 'b'):
+        bench.dump_outputs(arrays, str(tmp_path / d))
+    got = {n: np.load(tmp_path / 'a' / (n + '.npy')) for n in arrays}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got['loss'].shape == () and float(got['loss']) == 2.5
+    assert np.array_equal(got['params'], np.arange(10.0, dtype=np.float32).reshape(2, 5))
+    flat = big.float().reshape(-1).numpy()
+    assert got['big'].shape == (bench.DUMP_MAX_ELEMENTS,) and np.isin(got['big'], flat).all()
+    assert np.array_equal(got['big'], np.load(tmp_path / 'b' / 'big.npy'))
+    with pytest.raises(ValueError):              # more than 64 MB in all is refused before anything is written
+        bench.dump_outputs({'a%d' % i: big for i in range(9)}, str(tmp_path / 'c'))
+    assert not (tmp_path / 'c').exists()
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_only_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps N --warmup W` without --full: the headline fields (the line reports N timed steps), none of the blocks that take
+    runs of their own; --dump-outputs writes the last step's loss and parameters in float32."""
+    if not torch.cuda.is_available():
+        pytest.skip('needs a GPU')
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1',
+                          '--dump-outputs', str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert (d['steps'], d['warmup'], d['unit'], d['dtype'], d['higher_is_better']) == (4, 1, 'samples/s', 'bf16', True)
+    assert d['ms_per_step'] > 0 and abs(d['value'] - 256 * 1e3 / d['ms_per_step']) <= 1e-6 * d['value']
+    for k in ('roofline', 'in_step_kernels', 'hamilton_gemm', 'layer_kernels', 'loss_variants', 'cfg5_stack', 'cfg2_layer', 'cpu_baseline',
+              'gpu_telemetry', 'energy_j_per_step'):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ['loss.npy', 'params.npy']
+    got = {n: np.load(tmp_path / (n + '.npy')) for n in ('loss', 'params')}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got['loss'].shape == () and np.isfinite(got['loss']) and float(got['loss']) > 0
+    assert got['params'].size >= d['config']['gemm_view']['parameters'] and np.isfinite(got['params']).all()
 
 
 @pytest.mark.gpu

@@ -8,7 +8,7 @@
 # 5. the default bench line (its cfg2_layer block) with the final library                     -> r06_bench_default_builder_run.json
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R; O=gpurun_out/r06c2; rm -rf $O; mkdir -p $O
-timeout 900 rocprofv3 --kernel-trace --stats -d $O -o ks_cfg2 --output-format csv -- python bench.py --steps 60 --warmup 3 --no-cpu-baseline --no-kernel-timing --workload cfg2_qconv1d_timit_b64_fp32 > $O/log_cfg2.txt 2>&1; echo "cfg2 trace rc=$?"
+timeout 900 rocprofv3 --kernel-trace --stats -d $O -o ks_cfg2 --output-format csv -- python bench.py --full --steps 60 --warmup 3 --no-cpu-baseline --no-kernel-timing --workload cfg2_qconv1d_timit_b64_fp32 > $O/log_cfg2.txt 2>&1; echo "cfg2 trace rc=$?"
 mv $O/ks_cfg2_kernel_stats.csv $O/r06_cfg2_kernel_stats.csv
 rm -f $O/*kernel_trace.csv $O/*agent_info.csv $O/*domain_stats.csv
 rm -rf gpurun_out/traffic
@@ -19,7 +19,7 @@ rm -rf gpurun_out/pmc
 ./tools/gpu_pmc.sh cfg2_qconv1d_timit_b64_fp32 $K "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY" "GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_ANY SQ_WAVES SQ_INSTS_SALU" > $O/r06_cfg2_${K}_pmc.txt 2>&1
 done
 python tools/ablate_cfg2.py 2>&1 | grep -v amdgpu.ids > $O/r06_cfg2_ablation.txt
-( time python bench.py > $O/r06_bench_default_builder_run.json 2> $O/bench_default.err ) 2> $O/bench_default.time
+( time python bench.py --full > $O/r06_bench_default_builder_run.json 2> $O/bench_default.err ) 2> $O/bench_default.time
 cat $O/bench_default.time | tail -3
 python - <<'PY'
 import json

@@ -17,12 +17,12 @@ R=$GRAFT_REPO_ROOT; cd $R; RTAG=${RTAG:-r05}; O=gpurun_out/$RTAG; rm -rf $O; mkd
 STEPS="${STEPS:-1 2 3 4 5 6 7 8 9 10}"
 has() { [[ " $STEPS " == *" $1 "* ]]; }
 if has 1; then
-timeout 900 rocprofv3 --kernel-trace --stats -d $O -o ks_qcnn --output-format csv -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-standalone > $O/log_qcnn.txt 2>&1; echo "qcnn trace rc=$?"
+timeout 900 rocprofv3 --kernel-trace --stats -d $O -o ks_qcnn --output-format csv -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-standalone > $O/log_qcnn.txt 2>&1; echo "qcnn trace rc=$?"
 python tools/trace_step.py $O/ks_qcnn_kernel_trace.csv --all > $O/${RTAG}_qcnn_step_timeline.txt
 mv $O/ks_qcnn_kernel_stats.csv $O/${RTAG}_qcnn_bf16_b256_kernel_stats.csv
 fi
 if has 2; then
-timeout 900 rocprofv3 --kernel-trace --stats -d $O -o ks_cfg2 --output-format csv -- python bench.py --steps 60 --warmup 3 --no-cpu-baseline --no-kernel-timing --workload cfg2_qconv1d_timit_b64_fp32 > $O/log_cfg2.txt 2>&1; echo "cfg2 trace rc=$?"
+timeout 900 rocprofv3 --kernel-trace --stats -d $O -o ks_cfg2 --output-format csv -- python bench.py --full --steps 60 --warmup 3 --no-cpu-baseline --no-kernel-timing --workload cfg2_qconv1d_timit_b64_fp32 > $O/log_cfg2.txt 2>&1; echo "cfg2 trace rc=$?"
 mv $O/ks_cfg2_kernel_stats.csv $O/${RTAG}_cfg2_kernel_stats.csv
 fi
 rm -f $O/*kernel_trace.csv $O/*agent_info.csv $O/*domain_stats.csv
@@ -50,11 +50,11 @@ if has 7; then
 python tools/ablate16.py c64 c32 c32to64 2>&1 | grep -v amdgpu.ids > $O/${RTAG}_ablation.txt
 fi
 if has 8; then
-( time python bench.py > $O/${RTAG}_bench_default_builder_run.json 2> $O/bench_default.err ) 2> $O/bench_default.time
-python bench.py --loss sum --no-extras --no-standalone --no-cpu-baseline > $O/${RTAG}_bench_sumloss_builder_run.json 2>/dev/null
-python bench.py --workload cfg5_stack_b32_fp16 --no-cpu-baseline > $O/${RTAG}_bench_cfg5_stack_builder_run.json 2>/dev/null
-for lay in channels_last native; do python bench.py --workload cfg3_body_qconv2d_b256_bf16 --layout $lay --no-cpu-baseline > $O/${RTAG}_bench_cfg3body_${lay}_builder_run.json 2>/dev/null; done
-QK_DP_FORCE_COLLECTIVES=1 python bench.py --gpus 1 --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-timing 2>/dev/null | grep "^{" > $O/${RTAG}_bench_one_rank_rccl_builder_run.json
+( time python bench.py --full > $O/${RTAG}_bench_default_builder_run.json 2> $O/bench_default.err ) 2> $O/bench_default.time
+python bench.py --full --loss sum --no-extras --no-standalone --no-cpu-baseline > $O/${RTAG}_bench_sumloss_builder_run.json 2>/dev/null
+python bench.py --full --workload cfg5_stack_b32_fp16 --no-cpu-baseline > $O/${RTAG}_bench_cfg5_stack_builder_run.json 2>/dev/null
+for lay in channels_last native; do python bench.py --full --workload cfg3_body_qconv2d_b256_bf16 --layout $lay --no-cpu-baseline > $O/${RTAG}_bench_cfg3body_${lay}_builder_run.json 2>/dev/null; done
+QK_DP_FORCE_COLLECTIVES=1 python bench.py --full --gpus 1 --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-timing 2>/dev/null | grep "^{" > $O/${RTAG}_bench_one_rank_rccl_builder_run.json
 cat $O/bench_default.time
 fi
 if has 9; then
@@ -70,9 +70,9 @@ fi
 if has 11; then
 # round 5: the LDS-DMA backward-weight kernel against its round-2..4 form, same box, alternating; the sf = 16 model; graph replay vs eager
 bash tools/r5_wgrad_ab.sh > /dev/null 2>&1; cp gpurun_out/r5/wgrad_ab.txt $O/${RTAG}_wgrad_ab.txt
-python bench.py --workload cfg3_qcnn_sf16_b256_bf16 --no-extras --no-cpu-baseline --no-standalone > $O/${RTAG}_bench_sf16_builder_run.json 2>/dev/null
+python bench.py --full --workload cfg3_qcnn_sf16_b256_bf16 --no-extras --no-cpu-baseline --no-standalone > $O/${RTAG}_bench_sf16_builder_run.json 2>/dev/null
 for i in 1 2; do
-python bench.py --no-extras --no-cpu-baseline --no-standalone 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('eager', d['ms_per_step'], d['gpu_telemetry']['mean_sclk_mhz'])"
-python bench.py --graph --no-extras --no-cpu-baseline --no-standalone 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('graph', d['ms_per_step'], d['gpu_telemetry']['mean_sclk_mhz'])"
+python bench.py --full --no-extras --no-cpu-baseline --no-standalone 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('eager', d['ms_per_step'], d['gpu_telemetry']['mean_sclk_mhz'])"
+python bench.py --full --graph --no-extras --no-cpu-baseline --no-standalone 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('graph', d['ms_per_step'], d['gpu_telemetry']['mean_sclk_mhz'])"
 done > $O/${RTAG}_graph_vs_eager.txt
 fi
