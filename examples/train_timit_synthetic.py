@@ -35,6 +35,8 @@ def main():
     ap.add_argument('--dropout', type=float, default=0.3)
     ap.add_argument('--l2', type=float, default=1e-5)
     ap.add_argument('--lr', type=float, default=5e-4)
+    ap.add_argument('--eval-every', type=int, default=0,
+                    help='every N steps: CTC cost and phone error rate (greedy decode) on a held-out synthetic batch (0: off)')
     args = ap.parse_args()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:          # started plainly: become the launcher of the ranks
         sys.exit(dp.spawn_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
@@ -62,6 +64,10 @@ def main():
     reducer = dp.BucketedAllReduce(flat, bucket_bytes=2 << 20)    # gradients leave in 2 MB buckets while the backward runs
     decay = flat.l2_decay()                                       # the l2 kernel regularisers, folded into the Adam kernel
     m, v = torch.zeros_like(flat.param), torch.zeros_like(flat.param)
+    if args.eval_every > 0:                                       # held-out batch, drawn after the training batch (which is unchanged)
+        xe = torch.randn(B, 4, 41, T, device=dev, generator=gen).to(torch.bfloat16)
+        le = torch.randint(0, 61, (B, 40), device=dev, generator=gen, dtype=torch.int32)
+        lle = torch.randint(10, 41, (B, 1), device=dev, generator=gen, dtype=torch.int32)
     for step in range(1, args.steps + 1):
         cost = model.ctc_loss(x, labels, input_length, label_length).mean()           # K.ctc_batch_cost, one HIP kernel
         cost.backward()
@@ -69,6 +75,10 @@ def main():
         F.adam_step(flat.param, flat.grad, m, v, step, lr=args.lr, grad_scale=1.0 / world, zero_grad=True, decay=decay)
         if rank == 0 and (step == 1 or step % 5 == 0 or step == args.steps):
             print('step %3d  ctc cost %.4f' % (step, float(cost)))
+        if args.eval_every > 0 and step % args.eval_every == 0 and rank == 0:
+            res = model.evaluate(xe, le, input_length, lle)           # eval mode, no graph, training flag restored
+            print('step %3d  held-out ctc cost %.4f  PER %.4f (%d / %d)'
+                  % (step, float(res.loss), float(res.per), int(res.errors), int(res.symbols)))
     if torch.distributed.is_initialized():
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -414,6 +414,43 @@ int qk_ctc_batch_cost(int32_t dtype, int32_t batch, int32_t frames, int32_t clas
                       int32_t max_label_len, const int32_t *input_length, const int32_t *label_length, float *cost, void *dy_pred,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- CTC decoding ----------------------------------------------------------------------------------------------------------
+ * K.ctc_decode and tf.edit_distance: what turns the posteriors of the validation function (models/interspeech_model.py:182-185 of
+ * the reference) into a phone error rate.  y_pred (batch, frames, classes) are softmax outputs in `dtype`, blank = classes - 1 (as in
+ * K.ctc_batch_cost), u[t][c] = log(y_pred[t][c] + 1e-7); only the first Tn = min(max(input_length[b], 0), frames) frames count
+ * (input_length: batch int32).  Tn = 0 gives an empty decode with log_prob 0.  All buffers are caller-owned device memory; the calls
+ * launch on `stream` and never synchronise.
+ *
+ * Greedy (K.ctc_decode(greedy=True) = tf.nn.ctc_greedy_decoder(merge_repeated=True)), one wave per sample: per frame the argmax
+ * over classes (the lowest index on ties), runs of equal symbols merged, then blanks dropped (a blank between two equal labels
+ * keeps both).  decoded (batch, frames) int32 padded with -1, decoded_len (batch), log_prob (batch) = -sum_{t < Tn} max_c u[t][c]
+ * (TensorFlow's neg_sum_logits, sign included, which Keras returns under the name log_prob).  classes <= 256.
+ *
+ * Beam search (K.ctc_decode(greedy=False, beam_width, top_paths) without a language model), one workgroup per sample: the CTC
+ * prefix beam search in lp[t][c] = u[t][c] - logsumexp_c u[t][.]; from the empty prefix, each frame keeps the beam_width best of
+ * the candidates (every beam staying, every beam extended by a non-blank class; an extension equal to a beam is merged into it),
+ * ordered by total log-probability, ties: stay before extension, then lower source rank, then lower class; -inf never enters.
+ * decoded (top_paths, batch, frames) int32 padded with -1, decoded_len (top_paths, batch), log_prob (batch, top_paths) float32 =
+ * log p(prefix | y_pred) NORMALISED (TensorFlow reports per-frame shifted scores; the ranking is the same).  Paths beyond the
+ * number of distinct beams are empty with log_prob -inf.  merge_repeated != 0 (TF 1.x default) collapses consecutive equal labels
+ * of the returned prefix on output; log_prob stays that of the uncollapsed prefix.  Limits: beam_width <= 128,
+ * top_paths <= beam_width, classes <= 256: QK_ERR_UNSUPPORTED beyond.  Workspace: qk_ctc_beam_workspace_bytes (one history word
+ * per sample, frame and beam slot).
+ *
+ * Edit distance (tf.edit_distance, unnormalised), one wave per pair: Levenshtein distance with unit costs between hypothesis b
+ * (hyp + b hyp_stride, hyp_len[b] tokens) and reference b (ref + b ref_stride, ref_len[b] tokens); lengths are clamped to
+ * [0, stride].  class_map (classes int32, or NULL) is applied to both first: a token t in [0, classes) becomes class_map[t], and is
+ * dropped when that is negative; other tokens are compared as they are.  distance (batch) int32; ref_len_out (batch, or NULL) =
+ * the reference length after the map.  ref_stride <= 1024 (QK_ERR_UNSUPPORTED beyond); any hypothesis length. */
+int qk_ctc_greedy_decode(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *input_length,
+                         int32_t *decoded, int32_t *decoded_len, float *log_prob, void *stream);
+size_t qk_ctc_beam_workspace_bytes(int32_t batch, int32_t frames, int32_t beam_width);
+int qk_ctc_beam_search_decode(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *input_length,
+                              int32_t beam_width, int32_t top_paths, int32_t merge_repeated, int32_t *decoded, int32_t *decoded_len,
+                              float *log_prob, void *workspace, size_t workspace_bytes, void *stream);
+int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
+                     const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *distance, int32_t *ref_len_out, void *stream);
+
 /* Softmax over the last axis of a (rows, cols <= 64) matrix, one wave per row -- the activation of the model's
  * TimeDistributed(Dense(62, activation='softmax')) output layer (models/interspeech_model.py:171-175) and its autodiff:
  *   fwd   y = softmax(logits + bias)          logits: fp32 (the GEMM's fp32 output), bias: fp32 or NULL, y: `dtype`

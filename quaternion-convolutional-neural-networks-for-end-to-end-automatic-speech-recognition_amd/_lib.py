@@ -115,6 +115,10 @@ SYMBOLS = {
                                        ctypes.c_float, ctypes.c_float, I32, ctypes.c_float, I32, _VP]),
     'qk_adam_step_dev': (ctypes.c_int, [_FP, _FP, _FP, _FP, _FP, _SZ, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_float, ctypes.c_float, _VP, ctypes.c_float, I32, _VP]),
+    'qk_ctc_greedy_decode': (ctypes.c_int, [I32, I32, I32, I32, _VP, _VP, _VP, _VP, _FP, _VP]),
+    'qk_ctc_beam_workspace_bytes': (_SZ, [I32, I32, I32]),
+    'qk_ctc_beam_search_decode': (ctypes.c_int, [I32, I32, I32, I32, _VP, _VP, I32, I32, I32, _VP, _VP, _FP, _VP, _SZ, _VP]),
+    'qk_edit_distance': (ctypes.c_int, [I32, _VP, I32, _VP, _VP, I32, _VP, _VP, I32, _VP, _VP, _VP]),
     'qk_softmax_rows_fwd': (ctypes.c_int, [I32, ctypes.c_int64, I32, _VP, _VP, _VP, _VP]),
     'qk_softmax_rows_bwd': (ctypes.c_int, [I32, ctypes.c_int64, I32, _VP, _VP, _VP, _VP, _VP]),
     'qk_dense_softmax_supported': (ctypes.c_int, [I32, ctypes.c_int64, I32, I32]),

@@ -1080,6 +1080,54 @@ int qk_ctc_batch_cost(int32_t dtype, int32_t batch, int32_t frames, int32_t clas
     return check_launch(rc, "qk_ctc_batch_cost");
 }
 
+int qk_ctc_greedy_decode(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *input_length,
+                         int32_t *decoded, int32_t *decoded_len, float *log_prob, void *stream)
+{
+    if (batch <= 0 || frames <= 0 || classes < 2 || dtype < QK_F32 || dtype > QK_F16) { set_error("ctc_greedy_decode: bad arguments (%d, %d, %d, dtype %d)", batch, frames, classes, dtype); return QK_ERR_INVALID_ARG; }
+    if (!y_pred || !input_length || !decoded || !decoded_len || !log_prob) { set_error("ctc_greedy_decode: NULL argument"); return QK_ERR_INVALID_ARG; }
+    if (classes > 256) { set_error("ctc_greedy_decode: more than 256 classes"); return QK_ERR_UNSUPPORTED; }
+    if ((long long)batch * frames * classes > INT_MAX) { set_error("ctc_greedy_decode: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
+    return check_launch(launch_ctc_greedy(dtype, batch, frames, classes, y_pred, input_length, decoded, decoded_len, log_prob,
+                                          (hipStream_t)stream), "qk_ctc_greedy_decode");
+}
+
+size_t qk_ctc_beam_workspace_bytes(int32_t batch, int32_t frames, int32_t beam_width)
+{
+    if (batch <= 0 || frames <= 0 || beam_width <= 0) return 0;
+    return ctc_beam_workspace_bytes(batch, frames, beam_width);
+}
+
+int qk_ctc_beam_search_decode(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *input_length,
+                              int32_t beam_width, int32_t top_paths, int32_t merge_repeated, int32_t *decoded, int32_t *decoded_len,
+                              float *log_prob, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (batch <= 0 || frames <= 0 || classes < 2 || beam_width < 1 || top_paths < 1 || dtype < QK_F32 || dtype > QK_F16) {
+        set_error("ctc_beam_search_decode: bad arguments (%d, %d, %d, beam %d, paths %d, dtype %d)", batch, frames, classes, beam_width, top_paths, dtype);
+        return QK_ERR_INVALID_ARG;
+    }
+    if (!y_pred || !input_length || !decoded || !decoded_len || !log_prob) { set_error("ctc_beam_search_decode: NULL argument"); return QK_ERR_INVALID_ARG; }
+    if (classes > 256 || beam_width > 128 || top_paths > beam_width) {
+        set_error("ctc_beam_search_decode: unsupported (classes %d <= 256, beam_width %d <= 128, top_paths %d <= beam_width)", classes, beam_width, top_paths);
+        return QK_ERR_UNSUPPORTED;
+    }
+    if ((long long)batch * frames * classes > INT_MAX || (long long)top_paths * batch * frames > INT_MAX) { set_error("ctc_beam_search_decode: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
+    const size_t need = ctc_beam_workspace_bytes(batch, frames, beam_width);
+    if (!workspace || workspace_bytes < need || !aligned(workspace, 4)) { set_error("ctc_beam_search_decode needs %zu workspace bytes, got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    return check_launch(launch_ctc_beam(dtype, batch, frames, classes, y_pred, input_length, beam_width, top_paths, merge_repeated,
+                                        decoded, decoded_len, log_prob, static_cast<int *>(workspace), (hipStream_t)stream),
+                        "qk_ctc_beam_search_decode");
+}
+
+int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
+                     const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *distance, int32_t *ref_len_out, void *stream)
+{
+    if (batch <= 0 || hyp_stride < 0 || ref_stride < 0 || (class_map && classes <= 0)) { set_error("edit_distance: bad arguments (%d, %d, %d, %d)", batch, hyp_stride, ref_stride, classes); return QK_ERR_INVALID_ARG; }
+    if (!hyp_len || !ref_len || !distance || (hyp_stride > 0 && !hyp) || (ref_stride > 0 && !ref)) { set_error("edit_distance: NULL argument"); return QK_ERR_INVALID_ARG; }
+    if (ref_stride > 1024) { set_error("edit_distance: reference longer than 1024 tokens (stride %d)", ref_stride); return QK_ERR_UNSUPPORTED; }
+    return check_launch(launch_edit_distance(batch, hyp, hyp_stride, hyp_len, ref, ref_stride, ref_len, class_map, class_map ? classes : 0,
+                                             distance, ref_len_out, (hipStream_t)stream), "qk_edit_distance");
+}
+
 int qk_softmax_rows_fwd(int32_t dtype, int64_t rows, int32_t cols, const float *logits, const float *bias, void *y, void *stream)
 {
     if (!logits || !y || rows < 0 || cols < 1 || cols > 64 || dtype < QK_F32 || dtype > QK_F16) { set_error("qk_softmax_rows_fwd: bad argument (1 <= cols <= 64)"); return QK_ERR_INVALID_ARG; }

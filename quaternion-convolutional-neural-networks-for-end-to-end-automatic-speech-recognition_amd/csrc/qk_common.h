@@ -341,6 +341,14 @@ int launch_hconv16_small(int dtype, const void *in, const void *wq, const float 
 size_t ctc_workspace_bytes(int B, int T, int Lmax);
 int launch_ctc(int dtype, int B, int T, int C, const void *pred, const int *labels, int Lmax, const int *in_len, const int *lab_len,
                float *cost, void *dpred, float *ws, hipStream_t stream);
+// CTC decoding and edit distance (qk_ctc_decode.hip)
+size_t ctc_beam_workspace_bytes(int B, int T, int W);
+int launch_ctc_greedy(int dtype, int B, int T, int C, const void *pred, const int *in_len, int *decoded, int *dlen, float *logp,
+                      hipStream_t stream);
+int launch_ctc_beam(int dtype, int B, int T, int C, const void *pred, const int *in_len, int W, int top, int merge, int *decoded,
+                    int *dlen, float *logp, int *hist, hipStream_t stream);
+int launch_edit_distance(int B, const int *hyp, int hs, const int *hl, const int *ref, int rs, const int *rl, const int *cmap,
+                         int classes, int *out, int *rlen_out, hipStream_t stream);
 int launch_relayout16(const void *src, void *dst, int n, int A, int B, hipStream_t stream);     // (n, A, B) -> (n, B, A), 16-bit
 struct PoolGeom { int batch, ih, iw, C, wh, ww, oh, ow; };
 int launch_maxpool(int dtype, bool backward, const void *x, const void *dy, void *out, const PoolGeom &g, hipStream_t stream);

@@ -175,6 +175,19 @@ class _Call(object):
             n = self._ws_bytes[('k', kop)] = int(getattr(L.lib(), self.ws_fn)(ctypes.byref(self.desc), kop))
         return n
 
+    def _prep_key(self, op):
+        """Key of this call's cached re-layout on the parameter: (operation, conj, dtype) names the layout of a kernel read in its
+        own (taps-major) order, whose taps, cq and fq follow from the parameter's shape.  A channel-major reading of the same
+        parameter (the first TimeDistributed dense layer's weight read in place as an (F, 1) convolution kernel,
+        qk_conv_desc_t.kernel_order) is a different layout of the same byte count, so its key also carries kernel_order, the taps,
+        cq and fq -- with the three-part key alone, a model that ran that reading in training and the plain dense layer in
+        evaluation handed each the other's layout."""
+        d = self.desc
+        key = ('f' if op == L.QK_OP_FWD else 't', int(d.conj) if hasattr(d, 'conj') else 1, int(d.dtype))
+        if getattr(d, 'kernel_order', L.QK_KERNEL_TAPS_MAJOR) != L.QK_KERNEL_TAPS_MAJOR:
+            key += (int(d.kernel_order), tuple(d.kernel), int(d.cq), int(d.fq))
+        return key
+
     def _ws(self, op, like, wparam=None):
         """Workspace of operation `op`.  `wparam`: the PARAMETER the kernel argument is (a long-lived leaf tensor).  When the
         workspace holds only the kernel's 16-bit re-layout, it is kept ON the parameter together with the tensor version it
@@ -191,7 +204,7 @@ class _Call(object):
             return None, 0
         if (wparam is not None and not self.static_buffers and n == self._kernel_only_bytes(op) and wparam.is_leaf
                 and wparam.requires_grad and _PREP_CACHE_ON):
-            key = ('f' if op == L.QK_OP_FWD else 't', int(self.desc.conj) if hasattr(self.desc, 'conj') else 1, int(self.desc.dtype))
+            key = self._prep_key(op)
             cache = wparam.__dict__.setdefault('_qk_prep', {})
             base = getattr(wparam, '_qk_flat_base', None)         # dp.FlatParams: the flat buffer this parameter is a view of --
             ver = (wparam._version, -1 if base is None else base._version)    # `.data` views do not share its version counter
@@ -1184,3 +1197,125 @@ def ctc_batch_cost(y_pred, labels, input_length, label_length, loss_scale=1.0):
     if not (loss_scale > 0 and math.isfinite(loss_scale)):
         raise ValueError('loss_scale must be a positive finite number')
     return _CtcFn.apply(y_pred.contiguous(), labels, input_length, label_length, float(loss_scale))
+
+
+# ---- CTC decoding (include/qk.h, "CTC decoding") ----------------------------------------------------------------------------------
+CTC_MAX_BEAM, CTC_MAX_CLASSES, EDIT_MAX_REF = 128, 256, 1024
+
+
+def _decode_args(y_pred, input_length, what):
+    _require_device(y_pred, what)
+    if y_pred.dim() != 3 or min(y_pred.shape) < 1:
+        raise ValueError('%s: y_pred must be a non-empty (B, T, C) tensor, got shape %s' % (what, tuple(y_pred.shape)))
+    b, t, c = y_pred.shape
+    if c < 2 or c > CTC_MAX_CLASSES:
+        raise ValueError('%s: %d classes; the decoders take 2 <= classes <= %d' % (what, c, CTC_MAX_CLASSES))
+    il = input_length
+    if not torch.is_tensor(il):
+        il = torch.as_tensor(il)
+    if il.numel() != b or (il.dim() == 2 and il.shape[1] != 1) or il.dim() > 2:
+        raise ValueError('%s: input_length must have shape (B,) or (B, 1), got %s' % (what, tuple(il.shape)))
+    if il.is_cuda and il.device != y_pred.device:
+        raise ValueError('%s: input_length is on %s, y_pred on %s' % (what, il.device, y_pred.device))
+    il = il.reshape(-1).to(device=y_pred.device, dtype=torch.int32).contiguous()
+    return y_pred.contiguous(), il
+
+
+def ctc_greedy_decode(y_pred, input_length):
+    """K.ctc_decode(y_pred, input_length, greedy=True) = tf.nn.ctc_greedy_decoder(merge_repeated=True) as one launch
+    (qk_ctc_greedy_decode).  y_pred (B, T, C) softmax outputs (float32 / bfloat16 / float16), blank = C - 1; only the first
+    min(max(input_length[b], 0), T) frames count.  Per frame the argmax class (lowest index on ties), runs merged, blanks dropped.
+
+    Returns (decoded (B, T) int32 padded with -1, decoded_len (B,) int32, log_prob (B,) float32) on y_pred's device, without a
+    host sync.  log_prob = -sum_t max_c log(y_pred[t][c] + 1e-7): TensorFlow's neg_sum_logits, sign included, which Keras passes
+    through under the name log_prob -- mirrored as is."""
+    y, il = _decode_args(y_pred, input_length, 'ctc_greedy_decode')
+    b, t, c = y.shape
+    dec = torch.empty((b, t), dtype=torch.int32, device=y.device)
+    dlen = torch.empty(b, dtype=torch.int32, device=y.device)
+    lp = torch.empty(b, dtype=torch.float32, device=y.device)
+    with _on_device(y.device):
+        rc = L.lib().qk_ctc_greedy_decode(_DTYPES[y.dtype], b, t, c, _ptr(y), _ptr(il), _ptr(dec), _ptr(dlen), _ptr(lp), _stream(y))
+    L.check(rc, 'qk_ctc_greedy_decode')
+    return dec, dlen, lp
+
+
+def ctc_beam_search_decode(y_pred, input_length, beam_width=100, top_paths=1, merge_repeated=True):
+    """K.ctc_decode(y_pred, input_length, greedy=False, beam_width, top_paths) -- a CTC prefix beam search without a language model,
+    one workgroup per sample (qk_ctc_beam_search_decode).  Per frame each beam stays (blank or repeat of its last label) or is
+    extended by a non-blank class; an extension equal to an existing beam is merged into it; the beam_width best candidates by total
+    log-probability are kept (ties: stay before extension, then lower source rank, then lower class).
+
+    Returns (decoded (top_paths, B, T) int32 padded with -1, decoded_len (top_paths, B) int32, log_prob (B, top_paths) float32),
+    paths in descending order of log_prob, without a host sync.  Deviations from TensorFlow: log_prob is the NORMALISED
+    log p(prefix | y_pred) (TensorFlow reports scores shifted per frame; the ranking is identical, every candidate consumes one emission
+    per frame); paths beyond the number of distinct beams come back empty with log_prob -inf (TensorFlow raises).
+    merge_repeated (True, the TF 1.x default Keras 2.x calls) collapses consecutive equal labels of the returned prefix; log_prob stays
+    that of the uncollapsed prefix.  Limits: beam_width <= 128, top_paths <= beam_width, C <= 256."""
+    beam_width, top_paths = int(beam_width), int(top_paths)
+    if not 1 <= beam_width <= CTC_MAX_BEAM:
+        raise ValueError('ctc_beam_search_decode: beam_width %d outside 1 .. %d' % (beam_width, CTC_MAX_BEAM))
+    if not 1 <= top_paths <= beam_width:
+        raise ValueError('ctc_beam_search_decode: top_paths %d outside 1 .. beam_width (%d)' % (top_paths, beam_width))
+    y, il = _decode_args(y_pred, input_length, 'ctc_beam_search_decode')
+    b, t, c = y.shape
+    dec = torch.empty((top_paths, b, t), dtype=torch.int32, device=y.device)
+    dlen = torch.empty((top_paths, b), dtype=torch.int32, device=y.device)
+    lp = torch.empty((b, top_paths), dtype=torch.float32, device=y.device)
+    n = int(L.lib().qk_ctc_beam_workspace_bytes(b, t, beam_width))
+    ws = torch.empty(n, dtype=torch.uint8, device=y.device)
+    with _on_device(y.device):
+        rc = L.lib().qk_ctc_beam_search_decode(_DTYPES[y.dtype], b, t, c, _ptr(y), _ptr(il), beam_width, top_paths, int(bool(merge_repeated)),
+                                               _ptr(dec), _ptr(dlen), _ptr(lp), _ptr(ws), n, _stream(y))
+    L.check(rc, 'qk_ctc_beam_search_decode')
+    return dec, dlen, lp
+
+
+def _token_args(seq, length, what, name):
+    if not torch.is_tensor(seq) or not seq.is_cuda:
+        raise RuntimeError('%s: got a CPU tensor for %s. Decoding runs only on the MI355X HIP path (libqk_hip.so); there is no CPU '
+                           'fallback.' % (what, name))
+    if seq.dim() != 2:
+        raise ValueError('%s: %s must be a (B, L) tensor, got shape %s' % (what, name, tuple(seq.shape)))
+    b = seq.shape[0]
+    ln = length if torch.is_tensor(length) else torch.as_tensor(length)
+    if ln.numel() != b:
+        raise ValueError('%s: %s length must have B = %d entries, got %d' % (what, name, b, ln.numel()))
+    return (seq.to(dtype=torch.int32).contiguous(),
+            ln.reshape(-1).to(device=seq.device, dtype=torch.int32).contiguous())
+
+
+def _edit_distance(hyp, hyp_len, ref, ref_len, class_map=None):
+    what = 'edit_distance'
+    h, hl = _token_args(hyp, hyp_len, what, 'hyp')
+    r, rl = _token_args(ref, ref_len, what, 'ref')
+    if h.device != r.device:
+        raise ValueError('%s: hyp on %s, ref on %s' % (what, h.device, r.device))
+    if h.shape[0] != r.shape[0]:
+        raise ValueError('%s: %d hypotheses, %d references' % (what, h.shape[0], r.shape[0]))
+    if r.shape[1] > EDIT_MAX_REF:
+        raise ValueError('%s: references of up to %d tokens are supported, got %d' % (what, EDIT_MAX_REF, r.shape[1]))
+    b = h.shape[0]
+    cm, classes = None, 0
+    if class_map is not None:
+        cm = torch.as_tensor(class_map).reshape(-1).to(device=h.device, dtype=torch.int32).contiguous()
+        classes = cm.numel()
+        if classes < 1:
+            raise ValueError('%s: empty class_map' % what)
+    dist = torch.empty(b, dtype=torch.int32, device=h.device)
+    rlen = torch.empty(b, dtype=torch.int32, device=h.device)
+    if b == 0:
+        return dist, rlen
+    with _on_device(h.device):
+        rc = L.lib().qk_edit_distance(b, _ptr(h), h.shape[1], _ptr(hl), _ptr(r), r.shape[1], _ptr(rl), _ptr(cm), classes, _ptr(dist),
+                                      _ptr(rlen), _stream(h))
+    L.check(rc, 'qk_edit_distance')
+    return dist, rlen
+
+
+def edit_distance(hyp, hyp_len, ref, ref_len, class_map=None):
+    """tf.edit_distance(normalize=False) per pair as one launch (qk_edit_distance): Levenshtein distance with unit costs between
+    hyp[b, :hyp_len[b]] and ref[b, :ref_len[b]] (device int tensors (B, Lh) / (B, Lr), Lr <= 1024, any Lh).  class_map (C,) int: a
+    token t in [0, C) becomes class_map[t] in both sequences and is dropped when that is -1 (e.g. the TIMIT 61 -> 39 folding).
+    Returns (B,) int32 on the device, without a host sync."""
+    return _edit_distance(hyp, hyp_len, ref, ref_len, class_map)[0]

@@ -417,3 +417,50 @@ def ctc_batch_cost(y_pred, labels, input_length, label_length, blank=None, loss_
     loss = F.ctc_loss(logp, labels.long(), input_length.reshape(-1).long(), label_length.reshape(-1).long(),
                       blank=blank, reduction='none', zero_infinity=False)
     return loss.reshape(-1, 1)
+
+
+def ctc_decode(y_pred, input_length, greedy=True, beam_width=100, top_paths=1, merge_repeated=True):
+    """K.ctc_decode(y_pred, input_length, greedy, beam_width, top_paths) on the device (functional.ctc_greedy_decode /
+    functional.ctc_beam_search_decode; semantics and the deviations from TensorFlow are documented there and in include/qk.h).
+    y_pred (B, T, C) softmax outputs, blank = C - 1; input_length (B,) or (B, 1).
+
+    Returns ([decoded_k (B, L_k) int64 padded with -1 for k < top_paths], log_prob), like Keras: L_k is the longest decode of path k
+    in the batch -- ONE device-to-host read of the lengths, inherent to Keras' data-dependent shape.  log_prob is (B, 1) for greedy
+    (-sum of the per-frame max log-probabilities, TensorFlow's sign) and (B, top_paths) for the beam search (normalised
+    log p(prefix | y_pred))."""
+    if greedy:
+        dec, dlen, lp = Fq.ctc_greedy_decode(y_pred, input_length)
+        dec, dlen, lp = dec.unsqueeze(0), dlen.unsqueeze(0), lp.reshape(-1, 1)
+    else:
+        dec, dlen, lp = Fq.ctc_beam_search_decode(y_pred, input_length, beam_width, top_paths, merge_repeated)
+    longest = dlen.max(dim=1).values.tolist()
+    return [dec[k, :, :int(n)].long() for k, n in enumerate(longest)], lp
+
+
+def _seq_lengths(seq, length):
+    if length is not None:
+        return length
+    return (seq >= 0).sum(dim=1)            # decodes are padded with -1 behind the labels
+
+
+def edit_distance(hyp, hyp_len, ref, ref_len, class_map=None, normalize=False):
+    """tf.edit_distance per pair on the device (functional.edit_distance): Levenshtein distance between hyp[b, :hyp_len[b]] and
+    ref[b, :ref_len[b]] after the optional class_map (entry -1 drops a class).  normalize=True divides by the reference length
+    after the map (float32; a distance over an empty reference gives inf, 0 / 0 gives nan, as in TensorFlow); otherwise int32.
+    hyp_len / ref_len may be None for -1-padded sequences."""
+    dist, rlen = Fq._edit_distance(hyp, _seq_lengths(hyp, hyp_len), ref, _seq_lengths(ref, ref_len), class_map)
+    if not normalize:
+        return dist
+    return dist.float() / rlen.float()
+
+
+def label_error_rate(decoded, decoded_len, labels, label_length, class_map=None):
+    """Label (phone) error rate of a batch of decodes against the reference labels, computed the way the paper's PER is:
+    sum_b edit_distance(decoded_b, labels_b) / sum_b len(labels_b), both after the optional class_map (C,) int (entry -1 drops the
+    class, e.g. the TIMIT 61 -> 39 folding).  decoded (B, L) int, -1-padded (decoded_len may then be None); labels (B, Lmax) int,
+    label_length (B,) or (B, 1).  Returns (errors, ref_symbols, per) as 0-dim device tensors (int64, int64, float32): no host sync."""
+    if torch.is_tensor(labels) and torch.is_tensor(decoded):
+        labels = labels.to(decoded.device)
+    dist, rlen = Fq._edit_distance(decoded, _seq_lengths(decoded, decoded_len), labels, label_length, class_map)
+    errors, symbols = dist.long().sum(), rlen.long().sum()
+    return errors, symbols, errors.float() / symbols.float()

@@ -8,12 +8,17 @@ n/2 convs of 2*sf filters (PReLU + Dropout after each) -> Permute/reshape to (B,
 quat_init); only the quaternion branch (`d.model == 'quaternion'`) is built.
 """
 
+import collections
+
 import torch
 
 from .. import _lib as L
 from ..complexnn import QuaternionConv2D, QuaternionDense
 from ..keras_like import Layer, regularizers
-from ..layers import Dense, Dropout, MaxPooling2D, PReLU, TimeDistributed, ctc_batch_cost
+from ..layers import Dense, Dropout, MaxPooling2D, PReLU, TimeDistributed, ctc_batch_cost, ctc_decode, label_error_rate
+
+# TimitQCNN.evaluate: mean CTC cost, edit operations and reference symbols summed over the batch, their ratio (the PER), the decodes
+EvalResult = collections.namedtuple('EvalResult', 'loss errors symbols per decoded log_prob')
 
 
 class TimitQCNN(torch.nn.Module):
@@ -351,6 +356,45 @@ class TimitQCNN(torch.nn.Module):
                 return loss
             return ctc_batch_cost(self.pred(feats), labels, input_length, label_length, loss_scale=loss_scale).mean()
         return self.ctc_loss(x, labels, input_length, label_length, loss_scale=loss_scale).mean()
+
+    # ---- validation: decoding and phone error rate ------------------------------------------------------------------------------
+    def _inference(self, fn):
+        """fn() in inference mode: dropout off (no dropout-seed draw), no autograd graph, the module's training flag restored."""
+        was = self.training
+        self.train(False)
+        try:
+            with torch.no_grad():
+                return fn()
+        finally:
+            self.train(was)
+
+    def decode(self, x, input_length=None, greedy=True, beam_width=100, top_paths=1, merge_repeated=True):
+        """K.ctc_decode of the eval-mode posteriors self(x) (the reference's val_function output, interspeech_model.py:182-185):
+        layers.ctc_decode's ([decoded_k (B, L_k) int64, -1-padded] * top_paths, log_prob).  The model keeps the T frames of its
+        input through the body, so input_length defaults to T for every sample."""
+        def run():
+            y = self(x)
+            il = input_length if input_length is not None else torch.full((y.shape[0],), y.shape[1], dtype=torch.int32, device=y.device)
+            return ctc_decode(y, il, greedy=greedy, beam_width=beam_width, top_paths=top_paths, merge_repeated=merge_repeated)
+        return self._inference(run)
+
+    def evaluate(self, x, labels, input_length, label_length, greedy=True, beam_width=100, class_map=None):
+        """One validation batch from ONE eval-mode forward: EvalResult(loss = mean CTC cost (what ctc_mean_loss gives in eval mode),
+        errors / symbols = edit operations and reference labels summed over the batch, per = errors / symbols, decoded = the best
+        path (B, L) int64 -1-padded, log_prob).  class_map (62,) int folds classes before the edit distance (-1 drops one).  The
+        counts are device tensors: nothing waits for the GPU except layers.ctc_decode's read of the decode lengths."""
+        def run():
+            self._features_only = True
+            try:
+                feats = self(x)
+            finally:
+                self._features_only = False
+            y = self.pred(feats)
+            loss = ctc_batch_cost(y, labels, input_length, label_length).mean()
+            decoded, log_prob = ctc_decode(y, input_length, greedy=greedy, beam_width=beam_width, top_paths=1)
+            errors, symbols, per = label_error_rate(decoded[0], None, labels, label_length, class_map)
+            return EvalResult(loss, errors, symbols, per, decoded[0], log_prob)
+        return self._inference(run)
 
     def regularization_loss(self):
         """Sum of the kernel regularisers (l2(d.l2) on every conv / dense kernel, interspeech_model.py:63,68,173):
