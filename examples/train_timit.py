@@ -1,0 +1,129 @@
+#!/usr/bin/env python
+"""Training loop for the TIMIT quaternion CNN on the TIMIT corpus itself: waveforms and .PHN transcriptions in, phone error rate out,
+all on one GPU.  The reference ships the model (models/interspeech_model.py:getTimitModel2D) and its input shape (4, 41, None) but no
+feature code; here the features come from qcnn_amd.features.quaternion_fbank (40 log mel energies + log energy, and their first three
+time derivatives as the quaternion components), computed on the device per batch.
+
+    python examples/train_timit.py --timit /path/to/TIMIT --steps 2000 --eval-every 200
+
+--timit DIR is walked for `*.WAV` + `*.PHN` pairs under TRAIN/ (training) and TEST/ (held out).  Utterances are batched by length;
+the loss is TimitQCNN.training_loss (mean CTC cost + the l2 terms) with the fused Adam kernel; every --eval-every steps the held-out
+CTC cost and the 39-class phone error rate (Lee & Hon folding) of one held-out batch are printed.
+"""
+import argparse
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
+import qcnn_amd  # noqa: E402,F401
+from qcnn_amd import dp, functional as F  # noqa: E402
+from qcnn_amd.data import TIMIT_PHONES_61, read_audio, read_phn, timit_61_to_39_class_map  # noqa: E402
+from qcnn_amd.features import quaternion_fbank  # noqa: E402
+from qcnn_amd.models import getTimitModel2D  # noqa: E402
+
+
+def load_split(root):
+    """[(int16 samples, int32 phone classes)] of every WAV / PHN pair under root, sorted by path."""
+    index = {p: c for c, p in enumerate(TIMIT_PHONES_61)}
+    utts = []
+    for d, _, files in sorted(os.walk(root)):
+        by_lower = {f.lower(): f for f in files}
+        for f in sorted(files):
+            stem, ext = os.path.splitext(f)
+            if ext.lower() != '.wav' or (stem + '.phn').lower() not in by_lower:
+                continue
+            wav = read_audio(os.path.join(d, f))
+            phones = read_phn(os.path.join(d, by_lower[(stem + '.phn').lower()]))
+            utts.append((wav, np.array([index[p] for p in phones], dtype=np.int32)))
+    return utts
+
+
+def find_split(root, name):
+    for d in os.listdir(root):
+        if d.lower() == name.lower() and os.path.isdir(os.path.join(root, d)):
+            return os.path.join(root, d)
+    raise SystemExit('%s: no %s/ directory' % (root, name))
+
+
+def length_batches(utts, batch):
+    """Index lists of up to `batch` utterances of similar length (sorted by sample count, then cut)."""
+    order = sorted(range(len(utts)), key=lambda i: len(utts[i][0]))
+    return [order[i:i + batch] for i in range(0, len(order), batch)]
+
+
+def to_device(utts, idx, dev, dtype):
+    """Features (quaternion_fbank, per-utterance normalisation), frame counts, padded labels and label lengths of one batch."""
+    n = [len(utts[i][0]) for i in idx]
+    wave = np.zeros((len(idx), max(n)), dtype=np.int16)
+    lab_len = [len(utts[i][1]) for i in idx]
+    labels = np.zeros((len(idx), max(lab_len)), dtype=np.int32)
+    for r, i in enumerate(idx):
+        wave[r, :n[r]] = utts[i][0]
+        labels[r, :lab_len[r]] = utts[i][1]
+    x, frame_lengths = quaternion_fbank(torch.from_numpy(wave).to(dev), torch.tensor(n, dtype=torch.int32), normalize='utterance',
+                                        dtype=dtype)
+    labels = torch.from_numpy(labels).to(dev)
+    label_length = torch.tensor(lab_len, dtype=torch.int32, device=dev)[:, None]
+    return x, frame_lengths[:, None], labels, label_length
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--timit', required=True, help='corpus root holding TRAIN/ and TEST/')
+    ap.add_argument('--steps', type=int, default=1000)
+    ap.add_argument('--batch', type=int, default=32, help='utterances per step')
+    ap.add_argument('--layers', type=int, default=10)
+    ap.add_argument('--filters', type=int, default=32)
+    ap.add_argument('--aact', default='none', choices=['none', 'prelu'])
+    ap.add_argument('--dropout', type=float, default=0.3)
+    ap.add_argument('--l2', type=float, default=1e-5)
+    ap.add_argument('--lr', type=float, default=5e-4)
+    ap.add_argument('--eval-every', type=int, default=100, help='held-out CTC cost and PER every N steps (0: off)')
+    ap.add_argument('--seed', type=int, default=0)
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+    torch.cuda.set_device(dev)
+    dtype = torch.bfloat16
+
+    train = load_split(find_split(args.timit, 'TRAIN'))
+    test = load_split(find_split(args.timit, 'TEST'))
+    if not train:
+        raise SystemExit('%s: no WAV / PHN pairs under TRAIN/' % args.timit)
+    print('%d training and %d held-out utterances' % (len(train), len(test)))
+    batches = length_batches(train, args.batch)
+    held_out = length_batches(test, args.batch)[0] if test else None
+    class_map = torch.from_numpy(timit_61_to_39_class_map())
+
+    d = types.SimpleNamespace(num_layers=args.layers, start_filter=args.filters, act='relu', aact=args.aact, dropout=args.dropout,
+                              l2=args.l2, model='quaternion', quat_init='quaternion')
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    model, _ = getTimitModel2D(d)
+    x0 = to_device(train, batches[0][:1], dev, dtype)[0]
+    with torch.no_grad():
+        model(x0)                                                 # build-on-first-call, like Keras
+    model.to(dev)
+    model.train()
+    flat = dp.FlatParams([p for p in model.parameters() if p.requires_grad])   # the l2 terms come through training_loss
+    m, v = torch.zeros_like(flat.param), torch.zeros_like(flat.param)
+    rng = np.random.RandomState(args.seed)
+    for step in range(1, args.steps + 1):
+        x, il, labels, ll = to_device(train, batches[rng.randint(len(batches))], dev, dtype)
+        loss = model.training_loss(x, labels, il, ll)
+        loss.backward()
+        F.adam_step(flat.param, flat.grad, m, v, step, lr=args.lr, zero_grad=True)
+        if step == 1 or step % 50 == 0 or step == args.steps:
+            print('step %5d  loss %.4f' % (step, float(loss)))
+        if args.eval_every > 0 and step % args.eval_every == 0 and held_out is not None:
+            xe, ile, le, lle = to_device(test, held_out, dev, dtype)
+            res = model.evaluate(xe, le, ile, lle, class_map=class_map)
+            print('step %5d  held-out ctc cost %.4f  PER(39) %.4f (%d / %d)'
+                  % (step, float(res.loss), float(res.per), int(res.errors), int(res.symbols)))
+
+
+if __name__ == '__main__':
+    main()

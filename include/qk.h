@@ -451,6 +451,36 @@ int qk_ctc_beam_search_decode(int32_t dtype, int32_t batch, int32_t frames, int3
 int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
                      const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *distance, int32_t *ref_len_out, void *stream);
 
+/* ---- Acoustic front end ----------------------------------------------------------------------------------------------------
+ * Waveforms -> the model's channels_first quaternion input out (batch, 4, F, frames), F = nfilt + (append_energy != 0): the
+ * python_speech_features logfbank + delta recipe (the reference's Input(shape=(4, 41, None)), models/interspeech_model.py:81, with
+ * nfilt = 40).  Per utterance b of n = min(max(lengths[b], 0), max_samples) samples of row b of wave (batch, max_samples):
+ *   pre-emphasis s'[0] = s[0], s'[i] = s[i] - preemph s[i-1]; n_b = qk_fbank_num_frames(n, frame_len, frame_step) frames of frame_len
+ *   samples every frame_step (zero padding to (n_b - 1) frame_step + frame_len), times the window (QK_WINDOW_RECT: 1, QK_WINDOW_HAMMING:
+ *   numpy.hamming(frame_len)); P = |rfft(frame, nfft)|^2 / nfft; rows 0..nfilt-1 = log(sum_k W[j][k] P[k]) with the triangles
+ *   W[j] of python_speech_features.get_filterbanks on the integer FFT bins mel_bins[j] <= mel_bins[j+1] <= mel_bins[j+2] (a HOST
+ *   array of nfilt + 2 entries in [0, nfft / 2]); row nfilt = log(sum_k P[k]) when append_energy; an exact zero becomes float64 eps
+ *   (2.22e-16) before the log.  Plane 0 = these static rows, planes 1..3 = delta, delta^2, delta^3 along time with
+ *   d[t] = sum_{k=-N..N} k x[clamp(t + k, 0, n_b - 1)] / (2 sum_{k=1..N} k^2), N = delta_n, clamped at each utterance's own frames.
+ *   Frames t >= n_b are 0 in every plane.  normalize = QK_FBANK_NORM_UTTERANCE: every (b, plane, row) becomes (x - mean) /
+ *   sqrt(var + 1e-8) over its n_b valid frames (biased variance); padding stays 0.
+ * Arithmetic is fp32 throughout (the static rows stay fp32 until the deltas are done); out_dtype (qk_dtype_t) is rounded once, at
+ * the store; the FFT's rounding error is ~1e-7 of the frame's norm in every bin, so a band far below the frame's energy has a
+ * proportionally larger error in its log.  wave_dtype: QK_WAVE_I16 (int16) or QK_WAVE_F32.  frame_lengths (batch) int32 receives n_b (a CTC input_length).
+ * frames >= qk_fbank_num_frames(max_samples, ...).  Limits (QK_ERR_UNSUPPORTED beyond): nfft a power of two in [256, 1024],
+ * 1 <= frame_len <= nfft, nfilt <= QK_FBANK_MAX_FILT, 1 <= delta_n <= 4.  Workspace: qk_fbank_workspace_bytes (the fp32 static rows,
+ * plus the fp32 planes when normalising).  Launches on `stream` and never synchronises. */
+#define QK_FBANK_MAX_FILT 128
+enum { QK_WAVE_F32 = 0, QK_WAVE_I16 = 1 };
+enum { QK_WINDOW_RECT = 0, QK_WINDOW_HAMMING = 1 };
+enum { QK_FBANK_NORM_NONE = 0, QK_FBANK_NORM_UTTERANCE = 1 };
+int32_t qk_fbank_num_frames(int64_t samples, int32_t frame_len, int32_t frame_step);
+size_t qk_fbank_workspace_bytes(int32_t batch, int32_t frames, int32_t rows, int32_t normalize);
+int qk_fbank_quaternion(int32_t wave_dtype, int32_t batch, int64_t max_samples, const void *wave, const int32_t *lengths, int32_t frames,
+                        int32_t frame_len, int32_t frame_step, int32_t nfft, float preemph, int32_t window, int32_t nfilt,
+                        const int32_t *mel_bins, int32_t append_energy, int32_t delta_n, int32_t normalize, int32_t out_dtype, void *out,
+                        int32_t *frame_lengths, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Softmax over the last axis of a (rows, cols <= 64) matrix, one wave per row -- the activation of the model's
  * TimeDistributed(Dense(62, activation='softmax')) output layer (models/interspeech_model.py:171-175) and its autodiff:
  *   fwd   y = softmax(logits + bias)          logits: fp32 (the GEMM's fp32 output), bias: fp32 or NULL, y: `dtype`

@@ -26,6 +26,10 @@ QK_DBG_NO_SMALL16 = 0x40000
 # graph-level A/B switches (include/qk.h): kept in the library's mask, acted on by models/interspeech_model.py and layers.py
 QK_DBG_NO_CONV_CHAIN, QK_DBG_NO_FUSED_PRELU, QK_DBG_NO_FUSED_DROPOUT, QK_DBG_NO_FUSED_CTC = 0x100000, 0x200000, 0x400000, 0x800000
 QK_DBG_NO_FUSED_FIRST, QK_DBG_NO_DENSE_IN_CHAIN, QK_DBG_NO_FUSED_SOFTMAX = 0x1000000, 0x2000000, 0x4000000
+QK_WAVE_F32, QK_WAVE_I16 = 0, 1                                  # acoustic front end (qk_fbank_quaternion)
+QK_WINDOW_RECT, QK_WINDOW_HAMMING = 0, 1
+QK_FBANK_NORM_NONE, QK_FBANK_NORM_UTTERANCE = 0, 1
+QK_FBANK_MAX_FILT = 128
 QK_ERR_INVALID_ARG, QK_ERR_UNSUPPORTED, QK_ERR_WORKSPACE, QK_ERR_LAUNCH = -1, -2, -3, -4
 QK_PATH_NAMES = {0: 'none', 1: 'mfma16', 2: 'mfma16_band', 3: 'fp32_mfma', 4: 'mfma16_point', 5: 'mfma16_small'}               # qk_last_path
 
@@ -119,6 +123,10 @@ SYMBOLS = {
     'qk_ctc_beam_workspace_bytes': (_SZ, [I32, I32, I32]),
     'qk_ctc_beam_search_decode': (ctypes.c_int, [I32, I32, I32, I32, _VP, _VP, I32, I32, I32, _VP, _VP, _FP, _VP, _SZ, _VP]),
     'qk_edit_distance': (ctypes.c_int, [I32, _VP, I32, _VP, _VP, I32, _VP, _VP, I32, _VP, _VP, _VP]),
+    'qk_fbank_num_frames': (I32, [ctypes.c_int64, I32, I32]),
+    'qk_fbank_workspace_bytes': (_SZ, [I32, I32, I32, I32]),
+    'qk_fbank_quaternion': (ctypes.c_int, [I32, I32, ctypes.c_int64, _VP, _VP, I32, I32, I32, I32, ctypes.c_float, I32, I32,
+                                           ctypes.POINTER(I32), I32, I32, I32, I32, _VP, _VP, _VP, _SZ, _VP]),
     'qk_softmax_rows_fwd': (ctypes.c_int, [I32, ctypes.c_int64, I32, _VP, _VP, _VP, _VP]),
     'qk_softmax_rows_bwd': (ctypes.c_int, [I32, ctypes.c_int64, I32, _VP, _VP, _VP, _VP, _VP]),
     'qk_dense_softmax_supported': (ctypes.c_int, [I32, ctypes.c_int64, I32, I32]),

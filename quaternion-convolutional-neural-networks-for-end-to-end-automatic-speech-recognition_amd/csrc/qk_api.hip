@@ -1,6 +1,7 @@
 // C-ABI front end (include/qk.h): descriptor validation, geometry, kernel selection.
 // No device allocation, no host synchronisation, nothing retained after return.
 #include <limits.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -1126,6 +1127,65 @@ int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, cons
     if (ref_stride > 1024) { set_error("edit_distance: reference longer than 1024 tokens (stride %d)", ref_stride); return QK_ERR_UNSUPPORTED; }
     return check_launch(launch_edit_distance(batch, hyp, hyp_stride, hyp_len, ref, ref_stride, ref_len, class_map, class_map ? classes : 0,
                                              distance, ref_len_out, (hipStream_t)stream), "qk_edit_distance");
+}
+
+int32_t qk_fbank_num_frames(int64_t samples, int32_t frame_len, int32_t frame_step)
+{
+    if (frame_len < 1 || frame_step < 1) return 0;
+    if (samples <= frame_len) return 1;
+    const long long n = 1 + (samples - frame_len + frame_step - 1) / frame_step;
+    return n > INT_MAX ? 0 : (int32_t)n;
+}
+
+size_t qk_fbank_workspace_bytes(int32_t batch, int32_t frames, int32_t rows, int32_t normalize)
+{
+    if (batch <= 0 || frames <= 0 || rows <= 0) return 0;
+    return fbank_workspace_bytes(batch, frames, rows, normalize == QK_FBANK_NORM_UTTERANCE);
+}
+
+int qk_fbank_quaternion(int32_t wave_dtype, int32_t batch, int64_t max_samples, const void *wave, const int32_t *lengths, int32_t frames,
+                        int32_t frame_len, int32_t frame_step, int32_t nfft, float preemph, int32_t window, int32_t nfilt,
+                        const int32_t *mel_bins, int32_t append_energy, int32_t delta_n, int32_t normalize, int32_t out_dtype, void *out,
+                        int32_t *frame_lengths, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (batch <= 0 || max_samples <= 0 || max_samples > INT_MAX || frames <= 0 || frame_len <= 0 || frame_step <= 0 || nfilt <= 0 ||
+        (wave_dtype != QK_WAVE_F32 && wave_dtype != QK_WAVE_I16) || (window != QK_WINDOW_RECT && window != QK_WINDOW_HAMMING) ||
+        (normalize != QK_FBANK_NORM_NONE && normalize != QK_FBANK_NORM_UTTERANCE) || out_dtype < QK_F32 || out_dtype > QK_F16 ||
+        !isfinite(preemph)) {
+        set_error("fbank_quaternion: bad arguments (batch %d, samples %lld, frames %d, frame %d / %d, nfilt %d, dtypes %d / %d, window %d, "
+                  "normalize %d)", batch, (long long)max_samples, frames, frame_len, frame_step, nfilt, wave_dtype, out_dtype, window, normalize);
+        return QK_ERR_INVALID_ARG;
+    }
+    if (!wave || !lengths || !mel_bins || !out || !frame_lengths) { set_error("fbank_quaternion: NULL argument"); return QK_ERR_INVALID_ARG; }
+    if (nfft < 256 || nfft > 1024 || (nfft & (nfft - 1)) || frame_len > nfft || nfilt > QK_FBANK_MAX_FILT || delta_n < 1 || delta_n > 4) {
+        set_error("fbank_quaternion: unsupported (nfft %d a power of two in [256, 1024] and >= frame_len %d, nfilt %d <= %d, delta_n %d in [1, 4])",
+                  nfft, frame_len, nfilt, QK_FBANK_MAX_FILT, delta_n);
+        return QK_ERR_UNSUPPORTED;
+    }
+    const int need_frames = qk_fbank_num_frames(max_samples, frame_len, frame_step);
+    if (frames < need_frames) { set_error("fbank_quaternion: %d frames < the %d of max_samples %lld", frames, need_frames, (long long)max_samples); return QK_ERR_INVALID_ARG; }
+    FbankGeom g;
+    g.B = batch; g.n_max = (int)max_samples; g.T = frames;
+    g.L = frame_len; g.S = frame_step; g.nfft = nfft;
+    g.nfilt = nfilt; g.F = nfilt + (append_energy ? 1 : 0);
+    g.window = window; g.preemph = preemph;
+    for (int j = 0; j < nfilt + 2; ++j) {
+        g.bins[j] = mel_bins[j];
+        if (mel_bins[j] < 0 || mel_bins[j] > nfft / 2 || (j > 0 && mel_bins[j] < mel_bins[j - 1])) {
+            set_error("fbank_quaternion: mel_bins[%d] = %d (must be non-decreasing in [0, nfft / 2])", j, mel_bins[j]);
+            return QK_ERR_INVALID_ARG;
+        }
+    }
+    if ((long long)batch * 4 * g.F * frames > INT_MAX || (long long)batch * max_samples > ((long long)1 << 40)) {
+        set_error("fbank_quaternion: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED;
+    }
+    g.tile = fbank_tile(frame_len, frame_step);
+    g.span = (g.tile - 1) * frame_step + frame_len;
+    const bool norm = normalize == QK_FBANK_NORM_UTTERANCE;
+    const size_t need = fbank_workspace_bytes(batch, frames, g.F, norm);
+    if (!workspace || workspace_bytes < need || !aligned(workspace, 16)) { set_error("fbank_quaternion needs %zu workspace bytes, got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    return check_launch(launch_fbank(wave_dtype, wave, lengths, g, delta_n, norm, out_dtype, out, frame_lengths, workspace,
+                                     (hipStream_t)stream), "qk_fbank_quaternion");
 }
 
 int qk_softmax_rows_fwd(int32_t dtype, int64_t rows, int32_t cols, const float *logits, const float *bias, void *y, void *stream)

@@ -349,6 +349,20 @@ int launch_ctc_beam(int dtype, int B, int T, int C, const void *pred, const int 
                     int *dlen, float *logp, int *hist, hipStream_t stream);
 int launch_edit_distance(int B, const int *hyp, int hs, const int *hl, const int *ref, int rs, const int *rl, const int *cmap,
                          int classes, int *out, int *rlen_out, hipStream_t stream);
+// acoustic front end (qk_fbank.hip)
+struct FbankGeom {
+    int B, n_max, T;            // utterances, samples per padded row, output frames
+    int L, S, nfft;             // frame length, frame step, FFT length
+    int nfilt, F;               // mel filters, rows (nfilt + 1 with the energy row)
+    int tile, span;             // frames per workgroup of the static kernel, samples it stages: (tile - 1) S + L
+    int window;                 // QK_WINDOW_*
+    float preemph;
+    int bins[QK_FBANK_MAX_FILT + 2];    // mel filter edges (FFT bins)
+};
+int fbank_tile(int L, int S);
+size_t fbank_workspace_bytes(int B, int T, int F, bool norm);
+int launch_fbank(int wave_dtype, const void *wave, const int *lengths, const FbankGeom &g, int N, bool norm, int out_dtype, void *out,
+                 int *frame_lengths, void *ws, hipStream_t stream);
 int launch_relayout16(const void *src, void *dst, int n, int A, int B, hipStream_t stream);     // (n, A, B) -> (n, B, A), 16-bit
 struct PoolGeom { int batch, ih, iw, C, wh, ww, oh, ow; };
 int launch_maxpool(int dtype, bool backward, const void *x, const void *dy, void *out, const PoolGeom &g, hipStream_t stream);

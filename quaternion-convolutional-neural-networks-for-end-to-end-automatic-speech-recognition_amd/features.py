@@ -1,0 +1,112 @@
+"""Acoustic front end: waveforms -> the TIMIT model's channels_first quaternion input (B, 4, nfilt + 1, T).
+
+The reference defines the input only by its shape, Input(shape=(4, 41, None)) (models/interspeech_model.py:81), and ships no feature
+code.  The recipe here is python_speech_features' `logfbank` + `delta` with nfilt = 40: 25 ms frames every 10 ms, 40 log mel
+filter-bank energies plus the log frame energy (the 41 rows), and the quaternion components r = static, i / j / k = first / second /
+third time derivative.  Everything runs on the device in fp32 (csrc/qk_fbank.hip); semantics and limits: include/qk.h, "Acoustic front
+end".  The input is data, so there is no autograd.
+"""
+import decimal
+import math
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import functional as F
+
+WINDOWS = {'rect': L.QK_WINDOW_RECT, 'hamming': L.QK_WINDOW_HAMMING}
+NORMALIZE = {None: L.QK_FBANK_NORM_NONE, 'utterance': L.QK_FBANK_NORM_UTTERANCE}
+
+
+def _round_half_up(x):
+    return int(decimal.Decimal(x).quantize(decimal.Decimal('1'), rounding=decimal.ROUND_HALF_UP))
+
+
+def frame_geometry(sample_rate=16000, winlen=0.025, winstep=0.01):
+    """(frame length, frame step) in samples: round-half-up of winlen / winstep times the rate (400 / 160 at 16 kHz)."""
+    return _round_half_up(winlen * sample_rate), _round_half_up(winstep * sample_rate)
+
+
+def num_frames(samples, sample_rate=16000, winlen=0.025, winstep=0.01):
+    """Frames of an utterance of `samples` samples: 1 up to one frame length, else 1 + ceil((samples - L) / S)."""
+    frame_len, frame_step = frame_geometry(sample_rate, winlen, winstep)
+    if samples <= frame_len:
+        return 1
+    return 1 + int(math.ceil((1.0 * samples - frame_len) / frame_step))
+
+
+def _mel_bins(nfilt, nfft, sample_rate, lowfreq, highfreq):
+    lo, hi = (2595 * np.log10(1 + f / 700.) for f in (lowfreq, highfreq))
+    mel = np.linspace(lo, hi, nfilt + 2)
+    return np.floor((nfft + 1) * (700 * (10 ** (mel / 2595.0) - 1)) / sample_rate)
+
+
+def mel_filterbank(nfilt=40, nfft=512, sample_rate=16000, lowfreq=0, highfreq=None):
+    """(nfilt, nfft // 2 + 1) float64: python_speech_features' get_filterbanks.  nfilt + 2 points evenly spaced in mel
+    (2595 log10(1 + f / 700)) from lowfreq to highfreq (default sample_rate / 2) are floored to FFT bins b; filter j rises from 0 at
+    b[j] to 1 at b[j+1] and falls back to 0 at b[j+2].  The device kernel builds its tables from the same bins."""
+    b = _mel_bins(nfilt, nfft, sample_rate, lowfreq, highfreq if highfreq is not None else sample_rate / 2)
+    fb = np.zeros((nfilt, nfft // 2 + 1))
+    for j in range(nfilt):
+        lo, mid, hi = b[j], b[j + 1], b[j + 2]
+        i = np.arange(int(lo), int(mid))
+        fb[j, i] = (i - lo) / (mid - lo)
+        i = np.arange(int(mid), int(hi))
+        fb[j, i] = (hi - i) / (hi - mid)
+    return fb
+
+
+def quaternion_fbank(wave, lengths=None, sample_rate=16000, winlen=0.025, winstep=0.01, nfilt=40, nfft=512, lowfreq=0, highfreq=None,
+                     preemph=0.97, window='rect', delta_n=2, append_energy=True, normalize=None, dtype=torch.float32):
+    """Quaternion filter-bank features of a batch of waveforms, on the device.
+
+    wave: (B, n_max) or (n_max,) int16 / float32 CUDA tensor; lengths: samples per utterance (B,) (default n_max each; clamped to
+    [0, n_max]).  Per utterance: pre-emphasis, frames of winlen every winstep seconds (zero-padded), the window ('rect' or 'hamming'),
+    |rfft(frame, nfft)|^2 / nfft, nfilt log mel energies (+ the log frame energy when append_energy), exact zeros floored to float64
+    eps; then delta, delta^2, delta^3 over delta_n frames (python_speech_features.delta), edge-clamped at the utterance's own frames.
+    normalize='utterance' standardises every (utterance, plane, row) over its valid frames.
+
+    Returns (x, frame_lengths): x (B, 4, nfilt [+ 1], T) in `dtype` with T = num_frames(n_max) and frames t >= frame_lengths[b]
+    zero; frame_lengths (B,) int32, ready to serve as the CTC input_length.  Limits: nfft a power of two in [256, 1024] and at least
+    the frame length, nfilt <= 128, 1 <= delta_n <= 4."""
+    if window not in WINDOWS:
+        raise ValueError('quaternion_fbank: window must be one of %s, got %r' % (sorted(WINDOWS), window))
+    if normalize not in NORMALIZE:
+        raise ValueError("quaternion_fbank: normalize must be None or 'utterance', got %r" % (normalize,))
+    frame_len, frame_step = frame_geometry(sample_rate, winlen, winstep)
+    if frame_len < 1 or frame_step < 1:
+        raise ValueError('quaternion_fbank: winlen and winstep must give at least one sample (got %d / %d)' % (frame_len, frame_step))
+    if nfft not in (256, 512, 1024) or nfft < frame_len:
+        raise ValueError('quaternion_fbank: nfft %r must be 256, 512 or 1024 and at least the frame length (%d samples)'
+                         % (nfft, frame_len))
+    if not 1 <= nfilt <= L.QK_FBANK_MAX_FILT:
+        raise ValueError('quaternion_fbank: nfilt %r outside 1 .. %d' % (nfilt, L.QK_FBANK_MAX_FILT))
+    if not 1 <= delta_n <= 4:
+        raise ValueError('quaternion_fbank: delta_n %r outside 1 .. 4' % (delta_n,))
+    highfreq = sample_rate / 2 if highfreq is None else highfreq
+    if not 0 <= lowfreq < highfreq <= sample_rate / 2:
+        raise ValueError('quaternion_fbank: need 0 <= lowfreq < highfreq <= sample_rate / 2 (got %r, %r)' % (lowfreq, highfreq))
+    if not math.isfinite(preemph):
+        raise ValueError('quaternion_fbank: preemph must be finite')
+    if not torch.is_tensor(wave) or not wave.is_cuda:
+        raise RuntimeError('quaternion_fbank: got a CPU tensor. The acoustic front end runs only on the MI355X HIP path '
+                           '(libqk_hip.so); there is no CPU fallback.')
+    if wave.dtype not in (torch.int16, torch.float32):
+        raise TypeError('quaternion_fbank: waveforms must be int16 or float32, got %s' % wave.dtype)
+    if wave.dim() == 1:
+        wave = wave[None]
+    if wave.dim() != 2 or min(wave.shape) < 1:
+        raise ValueError('quaternion_fbank: wave must be a non-empty (B, samples) tensor, got shape %s' % (tuple(wave.shape),))
+    b, n_max = wave.shape
+    if lengths is None:
+        lengths = torch.full((b,), n_max, dtype=torch.int32, device=wave.device)
+    else:
+        lengths = torch.as_tensor(lengths)
+        if lengths.numel() != b:
+            raise ValueError('quaternion_fbank: lengths must have B = %d entries, got %d' % (b, lengths.numel()))
+        lengths = lengths.reshape(-1).to(device=wave.device, dtype=torch.int32)
+    bins = _mel_bins(nfilt, nfft, sample_rate, lowfreq, highfreq).astype(np.int64).tolist()
+    frames = num_frames(n_max, sample_rate, winlen, winstep)
+    return F.fbank_quaternion(wave, lengths, frames, frame_len, frame_step, nfft, preemph, WINDOWS[window], bins, append_energy, delta_n,
+                              NORMALIZE[normalize], dtype)

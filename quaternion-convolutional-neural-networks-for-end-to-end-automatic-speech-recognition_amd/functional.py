@@ -1319,3 +1319,40 @@ def edit_distance(hyp, hyp_len, ref, ref_len, class_map=None):
     token t in [0, C) becomes class_map[t] in both sequences and is dropped when that is -1 (e.g. the TIMIT 61 -> 39 folding).
     Returns (B,) int32 on the device, without a host sync."""
     return _edit_distance(hyp, hyp_len, ref, ref_len, class_map)[0]
+
+
+# ---- Acoustic front end (include/qk.h, "Acoustic front end") -------------------------------------------------------------------
+def fbank_quaternion(wave, lengths, frames, frame_len, frame_step, nfft, preemph, window, mel_bins, append_energy, delta_n, normalize,
+                     dtype):
+    """Waveforms -> (B, 4, F, frames) quaternion filter-bank features as one call of qk_fbank_quaternion (two launches, three when
+    normalising).  wave (B, n_max) int16 / float32 on the device, lengths (B,) int32 samples per utterance (same device); mel_bins a
+    host sequence of nfilt + 2 FFT bin edges; window / normalize are the QK_WINDOW_* / QK_FBANK_NORM_* codes.  Returns
+    (features in `dtype`, frame_lengths (B,) int32) without a host sync.  The user-facing entry point, with the recipe's parameters
+    in seconds and hertz, is qcnn_amd.features.quaternion_fbank."""
+    if not torch.is_tensor(wave) or not wave.is_cuda:
+        raise RuntimeError('fbank_quaternion: got a CPU tensor. The acoustic front end runs only on the MI355X HIP path (libqk_hip.so); '
+                           'there is no CPU fallback.')
+    if wave.dtype not in (torch.int16, torch.float32):
+        raise TypeError('fbank_quaternion: waveforms must be int16 or float32, got %s' % wave.dtype)
+    if dtype not in _DTYPES:
+        raise TypeError('fbank_quaternion: unsupported output dtype %s (float32, bfloat16, float16)' % dtype)
+    if wave.dim() != 2 or min(wave.shape) < 1:
+        raise ValueError('fbank_quaternion: wave must be a non-empty (B, samples) tensor, got shape %s' % (tuple(wave.shape),))
+    if lengths.device != wave.device or lengths.dtype != torch.int32 or lengths.shape != (wave.shape[0],):
+        raise ValueError('fbank_quaternion: lengths must be a (B,) int32 tensor on %s' % wave.device)
+    wave, lengths = wave.contiguous(), lengths.contiguous()
+    b, n_max = wave.shape
+    nfilt = len(mel_bins) - 2
+    rows = nfilt + (1 if append_energy else 0)
+    out = torch.empty((b, 4, rows, frames), dtype=dtype, device=wave.device)
+    flen = torch.empty(b, dtype=torch.int32, device=wave.device)
+    n = int(L.lib().qk_fbank_workspace_bytes(b, frames, rows, int(normalize)))
+    ws = torch.empty(n, dtype=torch.uint8, device=wave.device)
+    bins = (ctypes.c_int32 * len(mel_bins))(*[int(v) for v in mel_bins])
+    wd = L.QK_WAVE_I16 if wave.dtype == torch.int16 else L.QK_WAVE_F32
+    with _on_device(wave.device):
+        rc = L.lib().qk_fbank_quaternion(wd, b, n_max, _ptr(wave), _ptr(lengths), frames, frame_len, frame_step, nfft, float(preemph),
+                                         int(window), nfilt, bins, int(bool(append_energy)), int(delta_n), int(normalize), _DTYPES[dtype],
+                                         _ptr(out), _ptr(flen), _ptr(ws), n, _stream(wave))
+    L.check(rc, 'qk_fbank_quaternion')
+    return out, flen

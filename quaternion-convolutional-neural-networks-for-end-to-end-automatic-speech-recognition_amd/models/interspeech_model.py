@@ -378,6 +378,15 @@ class TimitQCNN(torch.nn.Module):
             return ctc_decode(y, il, greedy=greedy, beam_width=beam_width, top_paths=top_paths, merge_repeated=merge_repeated)
         return self._inference(run)
 
+    def transcribe(self, wave, lengths=None, greedy=True, beam_width=100, top_paths=1, **fbank_kw):
+        """Waveforms to phone decodes on the device: features.quaternion_fbank(wave, lengths, **fbank_kw) (the model's input, in the
+        parameters' dtype unless fbank_kw gives `dtype`), then decode() with input_length = the frame counts.  Returns decode()'s
+        ([decoded_k (B, L_k) int64, -1-padded] * top_paths, log_prob), in inference mode."""
+        from ..features import quaternion_fbank
+        fbank_kw.setdefault('dtype', next(self.parameters()).dtype)
+        x, frame_lengths = quaternion_fbank(wave, lengths, **fbank_kw)
+        return self.decode(x, frame_lengths, greedy=greedy, beam_width=beam_width, top_paths=top_paths)
+
     def evaluate(self, x, labels, input_length, label_length, greedy=True, beam_width=100, class_map=None):
         """One validation batch from ONE eval-mode forward: EvalResult(loss = mean CTC cost (what ctc_mean_loss gives in eval mode),
         errors / symbols = edit operations and reference labels summed over the batch, per = errors / symbols, decoded = the best
