@@ -9,6 +9,12 @@ time derivatives as the quaternion components), computed on the device per batch
 --timit DIR is walked for `*.WAV` + `*.PHN` pairs under TRAIN/ (training) and TEST/ (held out).  Utterances are batched by length;
 the loss is TimitQCNN.training_loss (mean CTC cost + the l2 terms) with the fused Adam kernel; every --eval-every steps the held-out
 CTC cost and the 39-class phone error rate (Lee & Hon folding) of one held-out batch are printed.
+
+--lm-order N (1-3; 0 = off) estimates an interpolated Kneser-Ney phone N-gram LM (qcnn_amd.lm.NgramLM) from the TRAIN transcripts,
+prints its held-out perplexity, and adds to every evaluation the PER(39) of the beam search (--beam-width) without and with the LM
+fused in (--lm-weight, --insertion-bonus).
+
+    python examples/train_timit.py --timit /path/to/TIMIT --eval-every 200 --lm-order 2 --lm-weight 0.5 --beam-width 16
 """
 import argparse
 import os
@@ -23,6 +29,7 @@ import qcnn_amd  # noqa: E402,F401
 from qcnn_amd import dp, functional as F  # noqa: E402
 from qcnn_amd.data import TIMIT_PHONES_61, read_audio, read_phn, timit_61_to_39_class_map  # noqa: E402
 from qcnn_amd.features import quaternion_fbank  # noqa: E402
+from qcnn_amd.lm import NgramLM  # noqa: E402
 from qcnn_amd.models import getTimitModel2D  # noqa: E402
 
 
@@ -84,6 +91,10 @@ def main():
     ap.add_argument('--lr', type=float, default=5e-4)
     ap.add_argument('--eval-every', type=int, default=100, help='held-out CTC cost and PER every N steps (0: off)')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--lm-order', type=int, default=0, choices=[0, 1, 2, 3], help='phone n-gram LM order for the beam search (0: off)')
+    ap.add_argument('--lm-weight', type=float, default=0.5)
+    ap.add_argument('--insertion-bonus', type=float, default=0.0)
+    ap.add_argument('--beam-width', type=int, default=16, help='beam width of the LM comparison')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
@@ -97,6 +108,11 @@ def main():
     batches = length_batches(train, args.batch)
     held_out = length_batches(test, args.batch)[0] if test else None
     class_map = torch.from_numpy(timit_61_to_39_class_map())
+    lm = None
+    if args.lm_order > 0:
+        lm = NgramLM.estimate([u[1] for u in train], len(TIMIT_PHONES_61), args.lm_order)
+        ppl = lm.perplexity([u[1] for u in test]) if test else float('nan')
+        print('%d-gram phone LM from %d TRAIN transcripts: held-out perplexity %.3f' % (args.lm_order, len(train), ppl))
 
     d = types.SimpleNamespace(num_layers=args.layers, start_filter=args.filters, act='relu', aact=args.aact, dropout=args.dropout,
                               l2=args.l2, model='quaternion', quat_init='quaternion')
@@ -123,6 +139,12 @@ def main():
             res = model.evaluate(xe, le, ile, lle, class_map=class_map)
             print('step %5d  held-out ctc cost %.4f  PER(39) %.4f (%d / %d)'
                   % (step, float(res.loss), float(res.per), int(res.errors), int(res.symbols)))
+            if lm is not None:
+                plain = model.evaluate(xe, le, ile, lle, greedy=False, beam_width=args.beam_width, class_map=class_map)
+                fused = model.evaluate(xe, le, ile, lle, greedy=False, beam_width=args.beam_width, class_map=class_map, lm=lm,
+                                       lm_weight=args.lm_weight, insertion_bonus=args.insertion_bonus)
+                print('step %5d  held-out beam %d PER(39) without LM %.4f  with %d-gram LM %.4f'
+                      % (step, args.beam_width, float(plain.per), args.lm_order, float(fused.per)))
 
 
 if __name__ == '__main__':

@@ -426,7 +426,7 @@ int qk_ctc_batch_cost(int32_t dtype, int32_t batch, int32_t frames, int32_t clas
  * keeps both).  decoded (batch, frames) int32 padded with -1, decoded_len (batch), log_prob (batch) = -sum_{t < Tn} max_c u[t][c]
  * (TensorFlow's neg_sum_logits, sign included, which Keras returns under the name log_prob).  classes <= 256.
  *
- * Beam search (K.ctc_decode(greedy=False, beam_width, top_paths) without a language model), one workgroup per sample: the CTC
+ * Beam search (K.ctc_decode(greedy=False, beam_width, top_paths) without a language model; an LM variant follows), one workgroup per sample: the CTC
  * prefix beam search in lp[t][c] = u[t][c] - logsumexp_c u[t][.]; from the empty prefix, each frame keeps the beam_width best of
  * the candidates (every beam staying, every beam extended by a non-blank class; an extension equal to a beam is merged into it),
  * ordered by total log-probability, ties: stay before extension, then lower source rank, then lower class; -inf never enters.
@@ -436,6 +436,21 @@ int qk_ctc_batch_cost(int32_t dtype, int32_t batch, int32_t frames, int32_t clas
  * of the returned prefix on output; log_prob stays that of the uncollapsed prefix.  Limits: beam_width <= 128,
  * top_paths <= beam_width, classes <= 256: QK_ERR_UNSUPPORTED beyond.  Workspace: qk_ctc_beam_workspace_bytes (one history word
  * per sample, frame and beam slot).
+ *
+ * Beam search with a phone n-gram language model (qk_ctc_beam_search_decode_lm): the same search, every candidate prefix l ranked by
+ *     S(l) = log p(l | y_pred) + lm_weight log P_LM(l) + insertion_bonus |l|
+ * in place of the total alone (the pb / pnb recursions, the merge, the tie rule and -inf exclusion are unchanged; P_LM(l) is the
+ * product of P(l_i | the preceding lm_order - 1 labels), <s>-padded on the left).  lm_eos != 0 re-ranks the final beams by
+ * S + lm_weight log P(</s> | l) before the top paths are read.  lm_table: device float32 natural-log probabilities
+ * (classes^(lm_order - 1), classes), finite or -inf; with V = classes - 1 (the blank's index), index V means <s> in a context and
+ * </s> as the event; the bigram context is the last label (V for the empty prefix), the trigram context last2 classes + last
+ * (V where missing), order 1 has a single row.  lm_weight must be finite and >= 0, insertion_bonus finite (QK_ERR_INVALID_ARG);
+ * lm_weight = 0 never reads the table, and lm_weight = insertion_bonus = 0 gives qk_ctc_beam_search_decode's results bit for
+ * bit.  log_prob (batch, top_paths) keeps its meaning (acoustic log p(prefix | y_pred)); score (batch, top_paths) float32 = the S
+ * the paths were ranked by; both -inf for empty paths.  merge_repeated collapses the output only: the LM scored the uncollapsed
+ * prefix.  Limits as above, and lm_order in 1 .. 3, lm_order 3 only for classes <= 64 (QK_ERR_UNSUPPORTED beyond); tables up to
+ * 64 KB live in LDS, larger ones stage the row of each beam's context per frame (beam_width x classes floats).  Workspace:
+ * qk_ctc_beam_workspace_bytes.
  *
  * Edit distance (tf.edit_distance, unnormalised), one wave per pair: Levenshtein distance with unit costs between hypothesis b
  * (hyp + b hyp_stride, hyp_len[b] tokens) and reference b (ref + b ref_stride, ref_len[b] tokens); lengths are clamped to
@@ -448,6 +463,11 @@ size_t qk_ctc_beam_workspace_bytes(int32_t batch, int32_t frames, int32_t beam_w
 int qk_ctc_beam_search_decode(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *input_length,
                               int32_t beam_width, int32_t top_paths, int32_t merge_repeated, int32_t *decoded, int32_t *decoded_len,
                               float *log_prob, void *workspace, size_t workspace_bytes, void *stream);
+int qk_ctc_beam_search_decode_lm(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred,
+                                 const int32_t *input_length, int32_t beam_width, int32_t top_paths, int32_t merge_repeated,
+                                 int32_t lm_order, const float *lm_table, float lm_weight, float insertion_bonus, int32_t lm_eos,
+                                 int32_t *decoded, int32_t *decoded_len, float *log_prob, float *score,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
                      const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *distance, int32_t *ref_len_out, void *stream);
 

@@ -1119,6 +1119,40 @@ int qk_ctc_beam_search_decode(int32_t dtype, int32_t batch, int32_t frames, int3
                         "qk_ctc_beam_search_decode");
 }
 
+int qk_ctc_beam_search_decode_lm(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred,
+                                 const int32_t *input_length, int32_t beam_width, int32_t top_paths, int32_t merge_repeated,
+                                 int32_t lm_order, const float *lm_table, float lm_weight, float insertion_bonus, int32_t lm_eos,
+                                 int32_t *decoded, int32_t *decoded_len, float *log_prob, float *score,
+                                 void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (batch <= 0 || frames <= 0 || classes < 2 || beam_width < 1 || top_paths < 1 || dtype < QK_F32 || dtype > QK_F16) {
+        set_error("ctc_beam_search_decode_lm: bad arguments (%d, %d, %d, beam %d, paths %d, dtype %d)", batch, frames, classes, beam_width, top_paths, dtype);
+        return QK_ERR_INVALID_ARG;
+    }
+    if (!(lm_weight >= 0.f) || !isfinite(lm_weight) || !isfinite(insertion_bonus)) {
+        set_error("ctc_beam_search_decode_lm: lm_weight %g must be finite and >= 0, insertion_bonus %g finite", (double)lm_weight, (double)insertion_bonus);
+        return QK_ERR_INVALID_ARG;
+    }
+    if (lm_order < 1 || lm_order > 3) { set_error("ctc_beam_search_decode_lm: lm_order %d outside 1 .. 3", lm_order); return QK_ERR_UNSUPPORTED; }
+    if (!y_pred || !input_length || !decoded || !decoded_len || !log_prob || !score || !lm_table) { set_error("ctc_beam_search_decode_lm: NULL argument"); return QK_ERR_INVALID_ARG; }
+    if (classes > 256 || beam_width > 128 || top_paths > beam_width) {
+        set_error("ctc_beam_search_decode_lm: unsupported (classes %d <= 256, beam_width %d <= 128, top_paths %d <= beam_width)", classes, beam_width, top_paths);
+        return QK_ERR_UNSUPPORTED;
+    }
+    if (lm_order == 3 && classes > 64) { set_error("ctc_beam_search_decode_lm: a trigram LM needs classes %d <= 64", classes); return QK_ERR_UNSUPPORTED; }
+    if (!ctc_beam_lm_supported(classes, beam_width, lm_order)) {
+        set_error("ctc_beam_search_decode_lm: the LM rows of %d beams x %d classes exceed the LDS budget", beam_width, classes);
+        return QK_ERR_UNSUPPORTED;
+    }
+    if ((long long)batch * frames * classes > INT_MAX || (long long)top_paths * batch * frames > INT_MAX) { set_error("ctc_beam_search_decode_lm: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
+    const size_t need = ctc_beam_workspace_bytes(batch, frames, beam_width);
+    if (!workspace || workspace_bytes < need || !aligned(workspace, 4)) { set_error("ctc_beam_search_decode_lm needs %zu workspace bytes, got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    return check_launch(launch_ctc_beam_lm(dtype, batch, frames, classes, y_pred, input_length, beam_width, top_paths, merge_repeated, lm_order,
+                                           lm_table, lm_weight, insertion_bonus, lm_eos, decoded, decoded_len, log_prob, score,
+                                           static_cast<int *>(workspace), (hipStream_t)stream),
+                        "qk_ctc_beam_search_decode_lm");
+}
+
 int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
                      const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *distance, int32_t *ref_len_out, void *stream)
 {

@@ -347,6 +347,10 @@ int launch_ctc_greedy(int dtype, int B, int T, int C, const void *pred, const in
                       hipStream_t stream);
 int launch_ctc_beam(int dtype, int B, int T, int C, const void *pred, const int *in_len, int W, int top, int merge, int *decoded,
                     int *dlen, float *logp, int *hist, hipStream_t stream);
+int ctc_beam_lm_supported(int C, int W, int order);
+int launch_ctc_beam_lm(int dtype, int B, int T, int C, const void *pred, const int *in_len, int W, int top, int merge, int order,
+                       const float *table, float alpha, float beta, int eos, int *decoded, int *dlen, float *logp, float *score, int *hist,
+                       hipStream_t stream);
 int launch_edit_distance(int B, const int *hyp, int hs, const int *hl, const int *ref, int rs, const int *rl, const int *cmap,
                          int classes, int *out, int *rlen_out, hipStream_t stream);
 // acoustic front end (qk_fbank.hip)

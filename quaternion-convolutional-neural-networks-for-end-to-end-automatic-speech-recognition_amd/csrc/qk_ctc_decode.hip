@@ -11,6 +11,11 @@
 //                    (32-bit score, 16-bit tie rank) -- the candidates are recomputed on every pass instead of being stored, so the
 //                    LDS footprint does not grow with the class count.  Every kept beam writes one history word per frame (source slot,
 //                    appended label) to the workspace; the paths are read back from it after the last frame.
+//                    LM = true fuses a phone n-gram LM (orders 1-3, dense natural-log table (C^(order-1), C)): candidates are ranked by
+//                    S = tot + F, F = alpha log P_LM(prefix) + beta |prefix| carried per beam in dynamic LDS with the label before
+//                    `last`.  The LM value of an extension (beam k, class c) comes from LDS on every select pass: the whole table when it
+//                    fits in 64 KB, otherwise the row of each live beam's context, staged once per frame.  With eos the final beams are
+//                    re-ranked by S + alpha log P(</s> | prefix) by a counting rank before the backtrack.
 //   k_edit_distance  one wave per pair: Levenshtein distance row by row over the hypothesis, vectorised over the reference, the
 //                    insertion chain along a row as a wave prefix-min: D[j] = j + min_{k <= j} (tmp[k] - k).
 #include "qk_common.h"
@@ -24,6 +29,10 @@ constexpr int BEAM_THREADS = 256;
 constexpr int kMaxBeam = 128;
 constexpr int kMaxClasses = 256;
 constexpr int kMaxEditRef = 1024;
+constexpr int kMaxLmOrder = 3;
+constexpr int kMaxLmTrigramClasses = 64;
+constexpr size_t kLmWholeTableBytes = 64 * 1024;      // the whole LM table goes to LDS up to this size, else per-beam context rows
+constexpr size_t kLmMaxDynLds = 128 * 1024 + 3 * 1024;  // dynamic LDS of the LM variant (the static part is ~20 KB of the 160 KB)
 
 __device__ __forceinline__ float lse2f(float a, float b)
 {
@@ -140,9 +149,33 @@ struct BeamSet {
 
 struct BeamGeom { int B, T, C, W, top, merge; };
 
-template <typename T>
+// LM fusion (k_ctc_beam<T, true> only).  whole: the table sits in LDS (else one row per live beam is staged per frame); use_tab =
+// alpha != 0 (alpha = 0: the table is never read and F = beta |prefix|).
+struct LmGeom {
+    const float *table;
+    float *score;
+    float alpha, beta;
+    int order, eos, whole, use_tab;
+};
+// dynamic LDS of the LM variant: per beam set F and the label before `last`, the final scores and ranks, then the table or the rows
+constexpr int kLmHeadWords = 2 * kMaxBeam * 2 + 2 * kMaxBeam;
+size_t lm_lds_bytes(int C, int W, int order, bool whole, bool use_tab)
+{
+    size_t tab = C;                                    // alpha = 0: a row of C floats keeps any (unused) table read in bounds
+    if (use_tab) {
+        size_t rows = 1;
+        for (int i = 1; i < order; ++i) rows *= (size_t)C;
+        tab = whole ? rows * C : (size_t)W * C;
+    }
+    return (kLmHeadWords + tab) * sizeof(float);
+}
+
+// F of an extension: F(l + c) = F(l) + alpha log P(c | ctx(l)) + beta, one rounding order everywhere it is evaluated
+__device__ __forceinline__ float lm_ext_bonus(float f, float lmv, float alpha, float beta) { return __fmaf_rn(alpha, lmv, f) + beta; }
+
+template <typename T, bool LM>
 __global__ void __launch_bounds__(BEAM_THREADS)
-k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const BeamGeom g, int *__restrict__ decoded,
+k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const BeamGeom g, const LmGeom lm, int *__restrict__ decoded,
            int *__restrict__ dlen, float *__restrict__ logp, int *__restrict__ hist)
 {
     __shared__ BeamSet bs[2];
@@ -162,10 +195,32 @@ k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const Bea
     const T *p = pred + (long long)b * g.T * C;
     int *hb = hist + (long long)b * g.T * W;
 
+    // LM state (dynamic LDS): lF[set][slot], lp2[set][slot] (label before `last`, -1 if none), fin / perm (final re-rank), tab
+    extern __shared__ float lm_dyn[];
+    float *lF = lm_dyn;
+    int *lp2 = reinterpret_cast<int *>(lm_dyn + 2 * kMaxBeam);
+    float *fin = lm_dyn + 4 * kMaxBeam;
+    int *perm = reinterpret_cast<int *>(lm_dyn + 5 * kMaxBeam);
+    float *tab = lm_dyn + kLmHeadWords;
+    const int V = C - 1;
+    // row offset of beam k's context in `tab` (whole table) or of its staged row; ctx: bigram last, trigram last2 C + last, V = <s>
+    auto lm_ctx = [&](int last, int p2) {
+        const int l1 = last < 0 ? V : last, l2 = p2 < 0 ? V : p2;
+        return lm.order == 1 ? 0 : (lm.order == 2 ? l1 : l2 * C + l1);
+    };
+
     if (tid == 0) {
         bs[0].pb[0] = 0.f; bs[0].pnb[0] = -INFINITY; bs[0].tot[0] = 0.f;
         bs[0].last[0] = -1; bs[0].len[0] = 0; bs[0].h[0] = 0ull; bs[0].ph[0] = 0ull;
         s_nb = 1;
+        if constexpr (LM) { lF[0] = 0.f; lp2[0] = -1; }
+    }
+    if constexpr (LM) {
+        if (lm.use_tab && lm.whole) {
+            int n = C;
+            for (int i = 1; i < lm.order; ++i) n *= C;
+            for (int i = tid; i < n; i += BEAM_THREADS) tab[i] = lm.table[i];
+        }
     }
     float yv[4];
 #pragma unroll
@@ -209,6 +264,16 @@ k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const Bea
         const int nb = s_nb;
         for (int i = tid; i < nb * (kMaxClasses / 32); i += BEAM_THREADS) emask[i] = 0u;
         if (tid == 0) l_count = 0;
+        const float *cF = lF + cur * kMaxBeam;
+        const int *cp2 = lp2 + cur * kMaxBeam;
+        if constexpr (LM) {
+            if (lm.use_tab && !lm.whole) {                 // stage the context row of every live beam: rows[k C + c]
+                for (int k = wave; k < nb; k += BEAM_THREADS / 64) {
+                    const float *src = lm.table + (long long)lm_ctx(S.last[k], cp2[k]) * C;
+                    for (int c = lane; c < C; c += 64) tab[k * C + c] = src[c];
+                }
+            }
+        }
         __syncthreads();
 
         // ---- 2./3. stay candidates, with the extension of the beam's parent merged in (if the parent is a beam)
@@ -233,21 +298,37 @@ k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const Bea
         __syncthreads();
 
         // ---- 4./5. radix select of the best W candidates: 8-bit digits from the top of the 48-bit key; candidates recomputed per pass
-        // visit(fn): fn(score, sec) for every candidate of this thread with a finite score
+        // visit(fn): fn(score, sec, acoustic) for every candidate of this thread with a finite score (score = acoustic without an LM)
         auto visit = [&](auto &&fn) {
             if (tid < nb) {
                 const float s = s_tot[tid];
-                if (s > -INFINITY) fn(s, (unsigned)tid << 8);
+                if constexpr (LM) {
+                    const float f = s + cF[tid];
+                    if (f > -INFINITY) fn(f, (unsigned)tid << 8, s);
+                } else {
+                    if (s > -INFINITY) fn(s, (unsigned)tid << 8, s);
+                }
             }
             for (int k = wave; k < nb; k += BEAM_THREADS / 64) {
                 const float pbk = S.pb[k], totk = S.tot[k];
                 const int lastk = S.last[k];
+                float fk = 0.f;
+                const float *row = tab;
+                if constexpr (LM) {
+                    fk = cF[k];
+                    row = tab + (!lm.use_tab ? 0 : lm.whole ? lm_ctx(lastk, cp2[k]) * C : k * C);
+                }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int c = lane + 64 * q;
                     if (c < CP && !((emask[k * (kMaxClasses / 32) + (c >> 5)] >> (c & 31)) & 1u)) {
                         const float s = (c == lastk ? pbk : totk) + lpr[q];
-                        if (s > -INFINITY) fn(s, 0x8000u | ((unsigned)k << 8) | (unsigned)c);
+                        if constexpr (LM) {
+                            const float f = s + lm_ext_bonus(fk, lm.use_tab ? row[c] : 0.f, lm.alpha, lm.beta);
+                            if (f > -INFINITY) fn(f, 0x8000u | ((unsigned)k << 8) | (unsigned)c, s);
+                        } else {
+                            if (s > -INFINITY) fn(s, 0x8000u | ((unsigned)k << 8) | (unsigned)c, s);
+                        }
                     }
                 }
             }
@@ -259,7 +340,7 @@ k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const Bea
             __syncthreads();
             if (sel_stop) break;                       // uniform: written before the barrier above
             const unsigned long long pre = sel_prefix >> (shift + 8);
-            visit([&](float s, unsigned sec) {
+            visit([&](float s, unsigned sec, float) {
                 const unsigned long long key = cand_key(s, sec);
                 if ((key >> (shift + 8)) == pre) atomicAdd(&hcount[(key >> shift) & 255u], 1u);
             });
@@ -310,11 +391,11 @@ k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const Bea
         }
         const unsigned long long thr = sel_prefix;
         const int K = sel_K;
-        visit([&](float s, unsigned sec) {
+        visit([&](float s, unsigned sec, float ac) {
             const unsigned long long key = cand_key(s, sec);
             if (key >= thr) {
                 const int pos = atomicAdd(&l_count, 1);
-                if (pos < kMaxBeam) { l_key[pos] = key; l_sec[pos] = sec; l_score[pos] = s; }
+                if (pos < kMaxBeam) { l_key[pos] = key; l_sec[pos] = sec; l_score[pos] = ac; }
             }
         });
         __syncthreads();
@@ -331,11 +412,17 @@ k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const Bea
                 N.pb[r] = s_pb[k]; N.pnb[r] = s_pnb[k]; N.tot[r] = s;
                 N.last[r] = S.last[k]; N.len[r] = S.len[k]; N.h[r] = S.h[k]; N.ph[r] = S.ph[k];
                 hb[(long long)t * W + r] = k;
+                if constexpr (LM) { lF[(cur ^ 1) * kMaxBeam + r] = cF[k]; lp2[(cur ^ 1) * kMaxBeam + r] = cp2[k]; }
             } else {
                 const int c = sec & 255;
                 N.pb[r] = -INFINITY; N.pnb[r] = s; N.tot[r] = s;
                 N.last[r] = c; N.len[r] = S.len[k] + 1; N.h[r] = hmix(S.h[k], c); N.ph[r] = S.h[k];
                 hb[(long long)t * W + r] = k | ((c + 1) << 16);
+                if constexpr (LM) {
+                    const float lmv = lm.use_tab ? tab[(!lm.use_tab ? 0 : lm.whole ? lm_ctx(S.last[k], cp2[k]) * C : k * C) + c] : 0.f;
+                    lF[(cur ^ 1) * kMaxBeam + r] = lm_ext_bonus(cF[k], lmv, lm.alpha, lm.beta);
+                    lp2[(cur ^ 1) * kMaxBeam + r] = S.last[k];
+                }
             }
         }
         if (tid == 0) s_nb = K;
@@ -346,15 +433,34 @@ k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const Bea
     // ---- backtrack the top paths through the history, merge repeats on request, pad with -1
     const BeamSet &F = bs[cur];
     const int nb = s_nb;
+    if constexpr (LM) {
+        // final S (+ alpha log P(</s> | prefix) with eos), then a counting rank over the nb beams; ties keep the lower slot first
+        if (tid < nb) {
+            float f = lF[cur * kMaxBeam + tid];
+            if (lm.eos && lm.use_tab)
+                f = __fmaf_rn(lm.alpha, lm.table[(long long)lm_ctx(F.last[tid], lp2[cur * kMaxBeam + tid]) * C + V], f);
+            fin[tid] = F.tot[tid] + f;
+        }
+        __syncthreads();
+        if (tid < nb) {
+            const unsigned long long my = cand_key(fin[tid], (unsigned)tid);
+            int r = 0;
+            for (int j = 0; j < nb; ++j) r += cand_key(fin[j], (unsigned)j) > my;
+            perm[r] = tid;
+        }
+        __syncthreads();
+    }
     if (tid < g.top) {
         const int pth = tid;
         int *row = decoded + ((long long)pth * g.B + b) * g.T;
         int L = 0;
-        float lp = -INFINITY;
+        float lp = -INFINITY, sc = -INFINITY;
         if (pth < nb) {
-            L = F.len[pth];
-            lp = F.tot[pth];
-            int s = pth, pos = L;
+            const int src = LM ? perm[pth] : pth;
+            L = F.len[src];
+            lp = F.tot[src];
+            if constexpr (LM) sc = fin[src];
+            int s = src, pos = L;
             for (int tt = Tn - 1; tt >= 0 && pos > 0; --tt) {
                 const int w = hb[(long long)tt * W + s];
                 const int lab = (w >> 16) - 1;
@@ -374,6 +480,7 @@ k_ctc_beam(const T *__restrict__ pred, const int *__restrict__ in_len, const Bea
         s_plen[pth] = L;
         dlen[(long long)pth * g.B + b] = L;
         logp[(long long)b * g.top + pth] = lp;
+        if constexpr (LM) lm.score[(long long)b * g.top + pth] = sc;
     }
     __syncthreads();
     for (int e = tid; e < g.top * g.T; e += BEAM_THREADS) {
@@ -484,13 +591,52 @@ int launch_ctc_beam(int dtype, int B, int T, int C, const void *pred, const int 
     if (C < 2 || C > kMaxClasses || W < 1 || W > kMaxBeam || top < 1 || top > W) return QK_ERR_UNSUPPORTED;
     BeamGeom g;
     g.B = B; g.T = T; g.C = C; g.W = W; g.top = top; g.merge = merge ? 1 : 0;
+    LmGeom lm = {};
     dim3 grid((unsigned)B), block(BEAM_THREADS);
     switch (dtype) {
-    case QK_F32: hipLaunchKernelGGL(k_ctc_beam<float>, grid, block, 0, stream, (const float *)pred, in_len, g, decoded, dlen, logp, hist); break;
-    case QK_BF16: hipLaunchKernelGGL(k_ctc_beam<bf16>, grid, block, 0, stream, (const bf16 *)pred, in_len, g, decoded, dlen, logp, hist); break;
-    case QK_F16: hipLaunchKernelGGL(k_ctc_beam<f16>, grid, block, 0, stream, (const f16 *)pred, in_len, g, decoded, dlen, logp, hist); break;
+    case QK_F32: hipLaunchKernelGGL((k_ctc_beam<float, false>), grid, block, 0, stream, (const float *)pred, in_len, g, lm, decoded, dlen, logp, hist); break;
+    case QK_BF16: hipLaunchKernelGGL((k_ctc_beam<bf16, false>), grid, block, 0, stream, (const bf16 *)pred, in_len, g, lm, decoded, dlen, logp, hist); break;
+    case QK_F16: hipLaunchKernelGGL((k_ctc_beam<f16, false>), grid, block, 0, stream, (const f16 *)pred, in_len, g, lm, decoded, dlen, logp, hist); break;
     default: return QK_ERR_INVALID_ARG;
     }
+    return hipGetLastError() == hipSuccess ? 0 : QK_ERR_LAUNCH;
+}
+
+int ctc_beam_lm_supported(int C, int W, int order)
+{
+    if (order < 1 || order > kMaxLmOrder || (order == 3 && C > kMaxLmTrigramClasses)) return 0;
+    const bool whole = lm_lds_bytes(C, W, order, true, true) - kLmHeadWords * sizeof(float) <= kLmWholeTableBytes;
+    return lm_lds_bytes(C, W, order, whole, true) <= kLmMaxDynLds;
+}
+
+int launch_ctc_beam_lm(int dtype, int B, int T, int C, const void *pred, const int *in_len, int W, int top, int merge, int order,
+                       const float *table, float alpha, float beta, int eos, int *decoded, int *dlen, float *logp, float *score, int *hist,
+                       hipStream_t stream)
+{
+    if (C < 2 || C > kMaxClasses || W < 1 || W > kMaxBeam || top < 1 || top > W || !ctc_beam_lm_supported(C, W, order))
+        return QK_ERR_UNSUPPORTED;
+    BeamGeom g;
+    g.B = B; g.T = T; g.C = C; g.W = W; g.top = top; g.merge = merge ? 1 : 0;
+    LmGeom lm;
+    lm.table = table; lm.score = score; lm.alpha = alpha; lm.beta = beta; lm.order = order; lm.eos = eos ? 1 : 0;
+    lm.use_tab = alpha != 0.f;
+    lm.whole = lm_lds_bytes(C, W, order, true, true) - kLmHeadWords * sizeof(float) <= kLmWholeTableBytes;
+    const size_t lds = lm_lds_bytes(C, W, order, lm.whole, lm.use_tab);
+    dim3 grid((unsigned)B), block(BEAM_THREADS);
+#define QK_BEAM_LM(TT)                                                                                                                  \
+    do {                                                                                                                                \
+        if (lds > 65536 && hipFuncSetAttribute((const void *)k_ctc_beam<TT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
+                                               (int)lds) != hipSuccess)                                                                 \
+            return QK_ERR_LAUNCH;                                                                                                       \
+        hipLaunchKernelGGL((k_ctc_beam<TT, true>), grid, block, lds, stream, (const TT *)pred, in_len, g, lm, decoded, dlen, logp, hist); \
+    } while (0)
+    switch (dtype) {
+    case QK_F32: QK_BEAM_LM(float); break;
+    case QK_BF16: QK_BEAM_LM(bf16); break;
+    case QK_F16: QK_BEAM_LM(f16); break;
+    default: return QK_ERR_INVALID_ARG;
+    }
+#undef QK_BEAM_LM
     return hipGetLastError() == hipSuccess ? 0 : QK_ERR_LAUNCH;
 }
 

@@ -1241,7 +1241,7 @@ def ctc_greedy_decode(y_pred, input_length):
 
 
 def ctc_beam_search_decode(y_pred, input_length, beam_width=100, top_paths=1, merge_repeated=True):
-    """K.ctc_decode(y_pred, input_length, greedy=False, beam_width, top_paths) -- a CTC prefix beam search without a language model,
+    """K.ctc_decode(y_pred, input_length, greedy=False, beam_width, top_paths) -- a CTC prefix beam search without a language model (ctc_beam_search_decode_lm fuses one),
     one workgroup per sample (qk_ctc_beam_search_decode).  Per frame each beam stays (blank or repeat of its last label) or is
     extended by a non-blank class; an extension equal to an existing beam is merged into it; the beam_width best candidates by total
     log-probability are kept (ties: stay before extension, then lower source rank, then lower class).
@@ -1269,6 +1269,60 @@ def ctc_beam_search_decode(y_pred, input_length, beam_width=100, top_paths=1, me
                                                _ptr(dec), _ptr(dlen), _ptr(lp), _ptr(ws), n, _stream(y))
     L.check(rc, 'qk_ctc_beam_search_decode')
     return dec, dlen, lp
+
+
+CTC_LM_MAX_TRIGRAM_CLASSES = 64
+
+
+def ctc_beam_search_decode_lm(y_pred, input_length, lm, beam_width=100, top_paths=1, merge_repeated=True, lm_weight=0.5,
+                              insertion_bonus=0.0, eos=True):
+    """CTC prefix beam search fused with a phone n-gram LM, one workgroup per sample (qk_ctc_beam_search_decode_lm).  Every candidate
+    prefix l is ranked by S(l) = log p(l | y_pred) + lm_weight log P_LM(l) + insertion_bonus |l| in place of the total alone (pb / pnb
+    recursions, merging and the tie rule as in ctc_beam_search_decode); eos=True re-ranks the final beams by S + lm_weight
+    log P(</s> | l).  lm: a qcnn_amd.lm.NgramLM over C - 1 labels (order 1 to 3; order 3 for C <= 64).  lm_weight must be finite
+    and >= 0, insertion_bonus finite; lm_weight = insertion_bonus = 0 returns ctc_beam_search_decode's results bit for bit.
+
+    Returns (decoded (top_paths, B, T) int32 padded with -1, decoded_len (top_paths, B) int32, log_prob (B, top_paths) float32 = the
+    acoustic log p(prefix | y_pred), score (B, top_paths) float32 = the S the paths were ranked by), without a host sync; empty paths
+    have -inf in both.  merge_repeated collapses the output; the LM scored the uncollapsed prefix."""
+    what = 'ctc_beam_search_decode_lm'
+    beam_width, top_paths = int(beam_width), int(top_paths)
+    if not 1 <= beam_width <= CTC_MAX_BEAM:
+        raise ValueError('%s: beam_width %d outside 1 .. %d' % (what, beam_width, CTC_MAX_BEAM))
+    if not 1 <= top_paths <= beam_width:
+        raise ValueError('%s: top_paths %d outside 1 .. beam_width (%d)' % (what, top_paths, beam_width))
+    lm_weight, insertion_bonus = float(lm_weight), float(insertion_bonus)
+    if not (math.isfinite(lm_weight) and lm_weight >= 0.0):
+        raise ValueError('%s: lm_weight must be finite and >= 0, got %r' % (what, lm_weight))
+    if not math.isfinite(insertion_bonus):
+        raise ValueError('%s: insertion_bonus must be finite, got %r' % (what, insertion_bonus))
+    order = int(lm.order)
+    if not 1 <= order <= 3:
+        raise ValueError('%s: LM order %d outside 1 .. 3' % (what, order))
+    if torch.is_tensor(y_pred) and y_pred.dim() == 3:          # LM / shape checks first: they need no device
+        c = y_pred.shape[2]
+        if lm.num_labels != c - 1:
+            raise ValueError('%s: the LM has %d labels, y_pred %d classes (%d labels + blank)' % (what, lm.num_labels, c, c - 1))
+        if order == 3 and c > CTC_LM_MAX_TRIGRAM_CLASSES:
+            raise ValueError('%s: a trigram LM needs C <= %d, got %d' % (what, CTC_LM_MAX_TRIGRAM_CLASSES, c))
+    y, il = _decode_args(y_pred, input_length, what)
+    b, t, c = y.shape
+    table = lm.table(y.device)
+    if tuple(table.shape) != (c ** (order - 1), c) or table.dtype != torch.float32:
+        raise ValueError('%s: LM table of shape %s %s, expected (%d, %d) float32' % (what, tuple(table.shape), table.dtype,
+                                                                                     c ** (order - 1), c))
+    dec = torch.empty((top_paths, b, t), dtype=torch.int32, device=y.device)
+    dlen = torch.empty((top_paths, b), dtype=torch.int32, device=y.device)
+    lp = torch.empty((b, top_paths), dtype=torch.float32, device=y.device)
+    score = torch.empty((b, top_paths), dtype=torch.float32, device=y.device)
+    n = int(L.lib().qk_ctc_beam_workspace_bytes(b, t, beam_width))
+    ws = torch.empty(n, dtype=torch.uint8, device=y.device)
+    with _on_device(y.device):
+        rc = L.lib().qk_ctc_beam_search_decode_lm(_DTYPES[y.dtype], b, t, c, _ptr(y), _ptr(il), beam_width, top_paths,
+                                                  int(bool(merge_repeated)), order, _ptr(table), lm_weight, insertion_bonus,
+                                                  int(bool(eos)), _ptr(dec), _ptr(dlen), _ptr(lp), _ptr(score), _ptr(ws), n, _stream(y))
+    L.check(rc, 'qk_ctc_beam_search_decode_lm')
+    return dec, dlen, lp, score
 
 
 def _token_args(seq, length, what, name):

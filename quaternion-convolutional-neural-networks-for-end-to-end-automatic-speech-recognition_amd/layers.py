@@ -419,7 +419,8 @@ def ctc_batch_cost(y_pred, labels, input_length, label_length, blank=None, loss_
     return loss.reshape(-1, 1)
 
 
-def ctc_decode(y_pred, input_length, greedy=True, beam_width=100, top_paths=1, merge_repeated=True):
+def ctc_decode(y_pred, input_length, greedy=True, beam_width=100, top_paths=1, merge_repeated=True, lm=None, lm_weight=0.5,
+               insertion_bonus=0.0, lm_eos=True):
     """K.ctc_decode(y_pred, input_length, greedy, beam_width, top_paths) on the device (functional.ctc_greedy_decode /
     functional.ctc_beam_search_decode; semantics and the deviations from TensorFlow are documented there and in include/qk.h).
     y_pred (B, T, C) softmax outputs, blank = C - 1; input_length (B,) or (B, 1).
@@ -427,10 +428,20 @@ def ctc_decode(y_pred, input_length, greedy=True, beam_width=100, top_paths=1, m
     Returns ([decoded_k (B, L_k) int64 padded with -1 for k < top_paths], log_prob), like Keras: L_k is the longest decode of path k
     in the batch -- ONE device-to-host read of the lengths, inherent to Keras' data-dependent shape.  log_prob is (B, 1) for greedy
     (-sum of the per-frame max log-probabilities, TensorFlow's sign) and (B, top_paths) for the beam search (normalised
-    log p(prefix | y_pred))."""
+    log p(prefix | y_pred)).
+
+    lm (a qcnn_amd.lm.NgramLM, beam search only: greedy=True with an LM raises ValueError) fuses a phone n-gram LM into the beam
+    (functional.ctc_beam_search_decode_lm, with lm_weight, insertion_bonus and lm_eos as its eos).  The log_prob slot then holds the
+    fused score S = log p(prefix | y_pred) + lm_weight log P_LM + insertion_bonus |prefix| (+ the </s> term), because that is what
+    ranks the paths."""
+    if lm is not None and greedy:
+        raise ValueError('ctc_decode: a language model needs the beam search (greedy=False)')
     if greedy:
         dec, dlen, lp = Fq.ctc_greedy_decode(y_pred, input_length)
         dec, dlen, lp = dec.unsqueeze(0), dlen.unsqueeze(0), lp.reshape(-1, 1)
+    elif lm is not None:
+        dec, dlen, _, lp = Fq.ctc_beam_search_decode_lm(y_pred, input_length, lm, beam_width, top_paths, merge_repeated, lm_weight,
+                                                        insertion_bonus, lm_eos)
     else:
         dec, dlen, lp = Fq.ctc_beam_search_decode(y_pred, input_length, beam_width, top_paths, merge_repeated)
     longest = dlen.max(dim=1).values.tolist()

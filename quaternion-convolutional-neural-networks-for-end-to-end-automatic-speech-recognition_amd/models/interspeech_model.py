@@ -368,30 +368,44 @@ class TimitQCNN(torch.nn.Module):
         finally:
             self.train(was)
 
-    def decode(self, x, input_length=None, greedy=True, beam_width=100, top_paths=1, merge_repeated=True):
+    def decode(self, x, input_length=None, greedy=True, beam_width=100, top_paths=1, merge_repeated=True, lm=None, lm_weight=0.5,
+               insertion_bonus=0.0):
         """K.ctc_decode of the eval-mode posteriors self(x) (the reference's val_function output, interspeech_model.py:182-185):
         layers.ctc_decode's ([decoded_k (B, L_k) int64, -1-padded] * top_paths, log_prob).  The model keeps the T frames of its
-        input through the body, so input_length defaults to T for every sample."""
+        input through the body, so input_length defaults to T for every sample.  lm (a qcnn_amd.lm.NgramLM, greedy=False only)
+        fuses a phone n-gram LM into the beam search; log_prob is then the fused score (layers.ctc_decode)."""
+        if lm is not None and greedy:
+            raise ValueError('decode: a language model needs the beam search (greedy=False)')
         def run():
             y = self(x)
             il = input_length if input_length is not None else torch.full((y.shape[0],), y.shape[1], dtype=torch.int32, device=y.device)
-            return ctc_decode(y, il, greedy=greedy, beam_width=beam_width, top_paths=top_paths, merge_repeated=merge_repeated)
+            return ctc_decode(y, il, greedy=greedy, beam_width=beam_width, top_paths=top_paths, merge_repeated=merge_repeated, lm=lm,
+                              lm_weight=lm_weight, insertion_bonus=insertion_bonus)
         return self._inference(run)
 
-    def transcribe(self, wave, lengths=None, greedy=True, beam_width=100, top_paths=1, **fbank_kw):
+    def transcribe(self, wave, lengths=None, greedy=True, beam_width=100, top_paths=1, lm=None, lm_weight=0.5, insertion_bonus=0.0,
+                   **fbank_kw):
         """Waveforms to phone decodes on the device: features.quaternion_fbank(wave, lengths, **fbank_kw) (the model's input, in the
-        parameters' dtype unless fbank_kw gives `dtype`), then decode() with input_length = the frame counts.  Returns decode()'s
-        ([decoded_k (B, L_k) int64, -1-padded] * top_paths, log_prob), in inference mode."""
+        parameters' dtype unless fbank_kw gives `dtype`), then decode() with input_length = the frame counts (and the optional LM).
+        Returns decode()'s ([decoded_k (B, L_k) int64, -1-padded] * top_paths, log_prob), in inference mode."""
+        if lm is not None and greedy:
+            raise ValueError('transcribe: a language model needs the beam search (greedy=False)')
         from ..features import quaternion_fbank
         fbank_kw.setdefault('dtype', next(self.parameters()).dtype)
         x, frame_lengths = quaternion_fbank(wave, lengths, **fbank_kw)
-        return self.decode(x, frame_lengths, greedy=greedy, beam_width=beam_width, top_paths=top_paths)
+        return self.decode(x, frame_lengths, greedy=greedy, beam_width=beam_width, top_paths=top_paths, lm=lm, lm_weight=lm_weight,
+                           insertion_bonus=insertion_bonus)
 
-    def evaluate(self, x, labels, input_length, label_length, greedy=True, beam_width=100, class_map=None):
+    def evaluate(self, x, labels, input_length, label_length, greedy=True, beam_width=100, class_map=None, lm=None, lm_weight=0.5,
+                 insertion_bonus=0.0):
         """One validation batch from ONE eval-mode forward: EvalResult(loss = mean CTC cost (what ctc_mean_loss gives in eval mode),
         errors / symbols = edit operations and reference labels summed over the batch, per = errors / symbols, decoded = the best
-        path (B, L) int64 -1-padded, log_prob).  class_map (62,) int folds classes before the edit distance (-1 drops one).  The
-        counts are device tensors: nothing waits for the GPU except layers.ctc_decode's read of the decode lengths."""
+        path (B, L) int64 -1-padded, log_prob).  class_map (62,) int folds classes before the edit distance (-1 drops one).  lm
+        (greedy=False only) decodes with a fused phone n-gram LM; log_prob is then the fused score.  The counts are device
+        tensors: nothing waits for the GPU except layers.ctc_decode's read of the decode lengths."""
+        if lm is not None and greedy:
+            raise ValueError('evaluate: a language model needs the beam search (greedy=False)')
+
         def run():
             self._features_only = True
             try:
@@ -400,7 +414,8 @@ class TimitQCNN(torch.nn.Module):
                 self._features_only = False
             y = self.pred(feats)
             loss = ctc_batch_cost(y, labels, input_length, label_length).mean()
-            decoded, log_prob = ctc_decode(y, input_length, greedy=greedy, beam_width=beam_width, top_paths=1)
+            decoded, log_prob = ctc_decode(y, input_length, greedy=greedy, beam_width=beam_width, top_paths=1, lm=lm,
+                                           lm_weight=lm_weight, insertion_bonus=insertion_bonus)
             errors, symbols, per = label_error_rate(decoded[0], None, labels, label_length, class_map)
             return EvalResult(loss, errors, symbols, per, decoded[0], log_prob)
         return self._inference(run)

@@ -3,6 +3,7 @@
 after warm-up, and TimitQCNN.evaluate against the eval-mode forward alone; prints one JSON line per measurement.
 
     python tools/ctc_decode_time.py [--reps 20] [--cpu-ref 0]        # --cpu-ref N: also time the float64 test reference on N utterances
+    python tools/ctc_decode_time.py --lm-order 2                     # only the beam search at W = 16 / 100, plain and with an n-gram LM
 
 The posteriors are peaky synthetic ones (softmax of scaled random logits, blank-heavy), like a trained model's output.
 """
@@ -41,10 +42,28 @@ def report(name, med_min, **kw):
     print(json.dumps(dict(name=name, median_ms=round(med_min[0], 4), min_ms=round(med_min[1], 4), **kw)), flush=True)
 
 
+def time_lm(args, y, il):
+    """Plain and LM-fused beam search at W = 16 and 100 in the same process, on an LM estimated from random phone sequences."""
+    from qcnn_amd.lm import NgramLM
+    B, T, C = y.shape
+    rng = np.random.RandomState(1)
+    corpus = [rng.randint(0, C - 1, size=rng.randint(20, 60)).tolist() for _ in range(2000)]
+    lm = NgramLM.estimate(corpus, C - 1, args.lm_order)
+    reps = max(3, args.reps // 2)
+    for W in (16, 100):
+        plain = timed(lambda: F.ctc_beam_search_decode(y, il, beam_width=W), reps)
+        fused = timed(lambda: F.ctc_beam_search_decode_lm(y, il, lm, beam_width=W, lm_weight=args.lm_weight, insertion_bonus=0.5), reps)
+        report('beam', plain, B=B, T=T, C=C, beam_width=W, dtype='bf16')
+        report('beam_lm', fused, B=B, T=T, C=C, beam_width=W, dtype='bf16', lm_order=args.lm_order,
+               ratio_to_plain=round(fused[0] / plain[0], 3))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--cpu-ref', type=int, default=0)
+    ap.add_argument('--lm-order', type=int, default=0, help='time the LM beam search (order 1-3) next to the plain one, and only those')
+    ap.add_argument('--lm-weight', type=float, default=0.5)
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     B, T, C = 256, 200, 62
@@ -53,6 +72,9 @@ def main():
     z[..., -1] += 3.0
     y = torch.softmax(torch.tensor(z, dtype=torch.float32), dim=-1).to(dev, torch.bfloat16)
     il = torch.full((B,), T, dtype=torch.int32, device=dev)
+    if args.lm_order:
+        time_lm(args, y, il)
+        return
     report('greedy', timed(lambda: F.ctc_greedy_decode(y, il), args.reps), B=B, T=T, C=C, dtype='bf16')
     for W, top in ((1, 1), (16, 1), (100, 1), (100, 3)):
         report('beam', timed(lambda: F.ctc_beam_search_decode(y, il, beam_width=W, top_paths=top), max(3, args.reps // 2)),
