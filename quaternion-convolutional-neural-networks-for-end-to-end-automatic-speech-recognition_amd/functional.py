@@ -1179,10 +1179,16 @@ def ctc_cost_and_grad(y_pred, labels, input_length, label_length):
     return cost, dpred
 
 
+def ctc_shape_supported(frames, classes, max_label_len):
+    """The shapes qk_ctc_batch_cost takes: C <= 256 classes, at most 127 labels per sample, and one sample's working set
+    (T + 8 Lmax + 4 + 2 C + 4 floats) within 64 KB of LDS."""
+    return classes <= 256 and max_label_len <= 127 and (frames + 8 * max_label_len + 4 + 2 * classes + 4) * 4 <= 64 * 1024
+
+
 def ctc_supported(y_pred, labels):
-    """qk_ctc_batch_cost takes a contiguous (B, T, C) device tensor with C <= 256 and at most 127 labels per sample."""
-    return (y_pred.is_cuda and y_pred.dtype in _DTYPES and y_pred.dim() == 3 and y_pred.shape[-1] <= 256 and y_pred.shape[0] > 0
-            and labels.dim() == 2 and labels.shape[1] <= 127 and (y_pred.shape[1] + 8 * labels.shape[1] + 4 + 2 * y_pred.shape[-1] + 4) * 4 <= 64 * 1024)
+    """qk_ctc_batch_cost takes a contiguous (B, T, C) device tensor of a shape ctc_shape_supported accepts."""
+    return (y_pred.is_cuda and y_pred.dtype in _DTYPES and y_pred.dim() == 3 and y_pred.shape[0] > 0 and labels.dim() == 2
+            and ctc_shape_supported(y_pred.shape[1], y_pred.shape[2], labels.shape[1]))
 
 
 def ctc_batch_cost(y_pred, labels, input_length, label_length, loss_scale=1.0):

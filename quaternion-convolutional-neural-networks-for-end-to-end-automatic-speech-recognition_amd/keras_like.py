@@ -322,10 +322,14 @@ class Layer(torch.nn.Module):
     def call(self, inputs):
         return inputs
 
-    def forward(self, inputs):
+    def ensure_built(self, input_shape, device):
+        """build(input_shape) with the weights on `device`, unless built already (Keras builds a layer on its first call)."""
         if not self.built:
-            self._build_device = inputs.device
-            self.build(tuple(inputs.shape))
+            self._build_device = device
+            self.build(tuple(input_shape))
+
+    def forward(self, inputs):
+        self.ensure_built(inputs.shape, inputs.device)
         return self.call(inputs)
 
     def compute_output_shape(self, input_shape):

@@ -178,6 +178,8 @@ def dense_softmax_ctc_mean(features, dense, labels, input_length, label_length, 
     """mean_b K.ctc_batch_cost(labels, TimeDistributed(dense)(features), input_length, label_length) for `features` (B, T, in_dim) and
     a built softmax `Dense` layer, through _DenseSoftmaxCtcMeanFn when the hand-written kernels take the shapes; None otherwise (the
     caller composes it from dense(features), ctc_batch_cost and .mean()).  loss_scale multiplies the gradient only."""
+    if not (loss_scale > 0 and math.isfinite(loss_scale)):
+        raise ValueError('loss_scale must be a positive finite number')
     if (not features.is_cuda or features.dim() != 3 or not dense.built or dense.kernel.dtype != torch.float32
             or activations.serialize(dense.activation) != 'softmax' or L.dbg(L.QK_DBG_NO_FUSED_SOFTMAX | L.QK_DBG_NO_FUSED_CTC)):
         return None
@@ -186,8 +188,7 @@ def dense_softmax_ctc_mean(features, dense, labels, input_length, label_length, 
     if not (b > 0 and x2.is_contiguous() and Fq.dense_softmax_supported(x2, dense.units) and dense.kernel.is_contiguous()
             and (dense.bias is None or dense.bias.is_contiguous())):
         return None
-    # (functional.ctc_supported on the posteriors this node will produce)
-    if not (labels.dim() == 2 and labels.shape[1] <= 127 and (t + 8 * labels.shape[1] + 4 + 2 * dense.units + 4) * 4 <= 64 * 1024):
+    if not (labels.dim() == 2 and Fq.ctc_shape_supported(t, dense.units, labels.shape[1])):      # (the posteriors this node produces)
         return None
     return _DenseSoftmaxCtcMeanFn.apply(x2, dense.kernel, dense.bias, labels, input_length, label_length, b, float(loss_scale))
 

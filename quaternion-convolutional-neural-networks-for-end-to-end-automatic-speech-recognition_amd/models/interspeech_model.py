@@ -13,9 +13,11 @@ import collections
 import torch
 
 from .. import _lib as L
+from .. import functional as Fq
 from ..complexnn import QuaternionConv2D, QuaternionDense
-from ..keras_like import Layer, regularizers
-from ..layers import Dense, Dropout, MaxPooling2D, PReLU, TimeDistributed, ctc_batch_cost, ctc_decode, label_error_rate
+from ..keras_like import Layer, activations, regularizers
+from ..layers import (Dense, Dropout, MaxPooling2D, PReLU, TimeDistributed, ctc_batch_cost, ctc_decode, dense_softmax_ctc_mean,
+                      label_error_rate)
 
 # TimitQCNN.evaluate: mean CTC cost, edit operations and reference symbols summed over the batch, their ratio (the PER), the decodes
 EvalResult = collections.namedtuple('EvalResult', 'loss errors symbols per decoded log_prob')
@@ -47,7 +49,7 @@ class TimitQCNN(torch.nn.Module):
         n_act = 1 + len(widths) + 3
         self.prelu = torch.nn.ModuleList([PReLU(shared_axes=[1, 0]) for _ in range(n_act)]) if aact == 'prelu' else None
         self.drop = Dropout(dropout)
-        self._drop_base, self._drop_calls, self._dev = 0, 0, None
+        self._drop_base = 0
         # optional: a one-element int32 device tensor (the step counter of functional.adam_step(step=<tensor>)) mixed into every
         # dropout seed ON THE DEVICE -- with it the launch arguments of a training step do not change from step to step, which
         # is what a captured graph needs (bench.ModelTrainStep.capture); fused post-op path only
@@ -68,266 +70,166 @@ class TimitQCNN(torch.nn.Module):
         rank = 0
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             rank = torch.distributed.get_rank()
-        self._drop_base, self._drop_calls = (base ^ (rank * 0x9E3779B1)) & 0xffffffff, 0
+        self._drop_base = (base ^ (rank * 0x9E3779B1)) & 0xffffffff
 
-    def _post(self, k, out_shape, dropout=True):
+    def _post(self, k, out_shape, device, dropout=True):
         """Post-op spec of activation slot k behind a quaternion layer whose (channels_first / TimeDistributed) output
         shape is `out_shape`: the PReLU slopes of self.prelu[k] (built here: (1, F, 1) behind a convolution, i.e. one
         per position of spatial axis 0 of the channels-last buffer; (1, 1) behind a dense layer) -- or alpha=None, the
-        relu form, for the aact='none' model -- and the dropout rate while training, with a fresh mask seed per call."""
+        relu form, for the aact='none' model -- and the dropout rate while training, with slot k's own mask seed."""
         rate = self.rate if (dropout and self.training) else 0.0
-        self._drop_calls += 1
-        seed = (self._drop_base + 7919 * self._drop_calls) & 0xffffffff
+        seed = (self._drop_base + 7919 * (k + 1)) & 0xffffffff
         if self.prelu is None:
             return dict(alpha=None, alpha_axis=-1, rate=rate, seed=seed, seed_dev=self.drop_step_dev if rate > 0 else None)
         pl = self.prelu[k]
-        if not pl.built:
-            pl._build_device = self._dev
-            pl.build(tuple(out_shape))
+        pl.ensure_built(out_shape, device)
         axis = 0 if pl.alpha.numel() > 1 else -1
         return dict(alpha=pl.alpha, alpha_axis=axis, rate=rate, seed=seed, seed_dev=self.drop_step_dev if rate > 0 else None)
 
+    def _link(self, layer, kernel, k, out_shape, device, fused, dropout=True, **geometry):
+        """`layer` as a functional.quaternion_conv_chain link (kernel, bias, kwargs) in activation slot k, its weight given as the
+        chain reads it: with the layer's own activation (linear / relu), or on the fused post-op path linear, followed by slot
+        k's post-op (_post)."""
+        if fused:
+            return kernel, layer.bias, dict(geometry, activation=None, post=self._post(k, out_shape, device, dropout))
+        return kernel, layer.bias, dict(geometry, activation=activations.serialize(layer.activation))
+
+    def _head_kernel(self, shape, device, dtype, in_chain):
+        """Permute((3,1,2)) + reshape + the first TimeDistributed(QuaternionDense) (interspeech_model.py:141-149) on the body
+        output (B, C, F, T) of `shape` WITHOUT the 367 MB transpose copy: feature c*F + f of time step t is o[b, c, f, t], so the
+        dense layer is a quaternion convolution with an (F, 1) 'valid' kernel over (F, T) -- same GEMM (K = F*C), same
+        conj(W) (x) x table.  Returns (kernel, geometry kwargs).  In a chain (`in_chain`) on 16-bit device tensors with
+        matrix-core widths the kernel is the dense PARAMETER itself, read in place as a channel-major kernel
+        (functional.quaternion_conv_chain: dense_kernel_size) -- no permuted copy, no re-layout launches, no permuted gradient
+        accumulation (8 small launches per step); otherwise the (F, 1, Cq, units) copy r[(cq*F + f), :] -> [f, 0, cq, :].
+        Parameters stay the reference's (in_q, units)."""
+        d0 = self.dense[0].layer
+        b, c, f, t = shape
+        d0.ensure_built((None, c * f), device)
+        if (in_chain and dtype in (torch.bfloat16, torch.float16) and device.type == 'cuda' and (c // 4) % 32 == 0
+                and (d0.r.shape[-1] // 4) % 32 == 0 and d0.r.is_contiguous()):
+            return d0.r, dict(conj=True, dense_kernel_size=(f, 1))
+        w = d0.r.view(c // 4, f, d0.r.shape[-1]).permute(1, 0, 2).unsqueeze(1).contiguous()
+        return w, dict(strides=1, padding='valid', dilation_rate=1, conj=True)
+
     def forward(self, x):
-        self._dev = x.device
+        return self.pred(self.features(x))
+
+    def features(self, x):
+        """The (B, T, 256) output of the last TimeDistributed(QuaternionDense) -- what the softmax output layer `pred` reads.
+
+        Which kernels run (fusable = chain_convs, a device input, fp32 / bf16 / fp16):
+        * fused post-op path -- every activation (+ Dropout) is the epilogue of the kernel that produces it (aact == 'prelu':
+          the kernel writes pre-activation and output, the next layer's backward-data applies the derivative; relu + dropout:
+          the kernel writes only y = dropout(relu(pre)), the consumer's backward multiplies by (y > 0) / (1 - rate)).  Taken with
+          PReLU when fusable and QK_DBG_NO_FUSED_PRELU is clear, and without PReLU when act == 'relu', training with rate > 0,
+          fusable and QK_DBG_NO_FUSED_DROPOUT is clear.  The head is always a chain link, even with fuse_head=False;
+          dense[1..2] join the chain in the relu form only, unless QK_DBG_NO_DENSE_IN_CHAIN.
+        * otherwise the plain chain -- no PReLU, no active dropout, chain_convs, a device input, more than one body
+          convolution, body activation linear or relu: the body convolutions as one autograd node,
+          the head its last link when fuse_head and the head's activation is linear or relu.
+        * otherwise layer by layer -- the head as the (F, 1) convolution on the kernel copy when fuse_head (device input),
+          Permute + reshape when not.
+        The first layer and its pooling run as one kernel per direction (conv_relu_pool without PReLU, conv_prelu_pool on the
+        fused path) where the kernel takes the geometry and QK_DBG_NO_FUSED_FIRST is clear."""
+        dev, relu_form = x.device, self.prelu is None
         fusable = self.chain_convs and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16, torch.float32)
-        if self.prelu is not None and fusable and not L.dbg(L.QK_DBG_NO_FUSED_PRELU):
-            return self._forward_fused_post(x)
-        # aact == 'none': relu layers with Dropout(d.dropout) behind every body convolution and the first two dense
-        # layers (interspeech_model.py:117-121,131-137,150-154) -- relu + dropout fused into the producing kernels
-        if (self.prelu is None and self.act == 'relu' and self.training and self.rate > 0 and fusable
-                and not L.dbg(L.QK_DBG_NO_FUSED_DROPOUT)):
-            return self._forward_fused_post(x)
-        o = self._first_layer_fused(x) if self.prelu is None else None
-        if o is None:
-            o = self._act(self.conv(x), 0)
-            o = self.pool(o)
-        k = 1
-        plain = self.prelu is None and not (self.training and self.rate > 0)
-        first = 0
-        if self.chain_convs and o.is_cuda and plain and len(self.convs) > 1:
-            o, with_head = self._convs_as_chain(o)
-            k += len(self.convs)
-            if with_head:                                    # first TimeDistributed dense ran inside the chain
-                k, first = k + 1, 1
+        if relu_form:
+            fused = fusable and self.act == 'relu' and self.training and self.rate > 0 and not L.dbg(L.QK_DBG_NO_FUSED_DROPOUT)
         else:
-            for c in self.convs:
-                o = self.drop(self._act(c(o), k))
-                k += 1
+            fused = fusable and not L.dbg(L.QK_DBG_NO_FUSED_PRELU)
+        if fused:
+            self._new_drop_base()
+
+        # first layer: conv (3,5) 'same' + MaxPooling2D((1,3), 'same') over frequency (interspeech_model.py:97-103).  The fused
+        # kernels never write the 41-bin activation; they read a plain channels_first buffer (how the reference's callers hold
+        # the features) plane by plane, and a channels-last buffer behind a channels_first view as it is.
+        c, pl = self.conv, self.pool
+        c.ensure_built(x.shape, dev)
+        xl, lay = (x, 'channels_first') if x.is_contiguous() else (x.movedim(1, -1), 'channels_last')
+        one_kernel = ((relu_form or fused) and x.is_cuda and x.dim() == 4 and c.padding == 'same' and c.strides == (1, 1)
+                      and c.dilation_rate == (1, 1) and c.internal_layout == 'channels_last' and pl.pool_size == (1, 3)
+                      and pl.strides == (1, 3) and pl.padding == 'same' and pl.data_format == 'channels_last'
+                      and not L.dbg(L.QK_DBG_NO_FUSED_FIRST))
+        if relu_form:
+            if one_kernel and activations.serialize(c.activation) == 'relu' and Fq.conv_relu_pool_supported(xl, c.kernel, 3, lay):
+                o = Fq.conv_relu_pool(xl, c.kernel, c.bias, 3, lay).movedim(-1, 1)
+            else:
+                o = pl(c(x))
+        elif fused:
+            po = self._post(0, c.compute_output_shape(tuple(x.shape)), dev, dropout=False)
+            if one_kernel and Fq.conv_prelu_pool_supported(xl, c.kernel, po['alpha'], po['alpha_axis'], 3, lay):
+                o = Fq.conv_prelu_pool(xl, c.kernel, c.bias, po['alpha'], po['alpha_axis'], 3, lay).movedim(-1, 1)
+            else:
+                o = pl(Fq.quaternion_conv(x, c.kernel, c.bias, strides=c.strides, padding=c.padding, data_format='channels_first',
+                                          dilation_rate=c.dilation_rate, activation=None, post=po))
+        else:
+            o = pl(self.prelu[0](c(x)))
+
+        # body: the n convolutions (interspeech_model.py:105-137), activation slots 1..n
+        chain = fused or (self.chain_convs and x.is_cuda and relu_form and not (self.training and self.rate > 0)
+                          and len(self.convs) > 1
+                          and all(activations.serialize(cv.activation) in ('linear', 'relu') for cv in self.convs))
+        shape, links, k = tuple(o.shape), [], 1
+        for cv in self.convs:
+            if chain:
+                cv.ensure_built(shape, dev)
+                shape = cv.compute_output_shape(shape)
+                links.append(self._link(cv, cv.kernel, k, shape, dev, fused, strides=cv.strides, padding=cv.padding,
+                                        dilation_rate=cv.dilation_rate))
+            else:
+                o = self.drop(self._act(cv(o), k))
+            k += 1
+
+        # head: Permute((3,1,2)) + reshape + the first TimeDistributed dense layer (interspeech_model.py:140-149)
+        d0, first = self.dense[0].layer, 0           # first: the first dense layer still to run
+        if fused or (chain and self.fuse_head and activations.serialize(d0.activation) in ('linear', 'relu')):
+            kernel, geometry = self._head_kernel(shape, dev, o.dtype, in_chain=True)
+            width = d0.r.shape[-1]
+            links.append(self._link(d0, kernel, k, (shape[0], shape[3], width), dev, fused, **geometry))
+            k, first = k + 1, 1
+            if fused and relu_form and not L.dbg(L.QK_DBG_NO_DENSE_IN_CHAIN):
+                # the second and third dense layers (interspeech_model.py:150-166) as 1 x 1 conj-convolution links of the same
+                # chain: relu (+ dropout behind the second) in the producing kernel, its derivative in the consumer's backward
+                for i in (1, 2):
+                    dn = self.dense[i].layer
+                    dn.ensure_built((None, width), dev)
+                    width = dn.r.shape[-1]
+                    links.append(self._link(dn, dn.r, k, (shape[0], shape[3], width), dev, fused, dropout=(i < 2)))
+                    k, first = k + 1, first + 1
+        if chain:
+            y = Fq.quaternion_conv_chain(o.movedim(1, -1), links)        # channels-last (B, F, T, C); (B, 1, T, units) with the head
+            o = y.reshape(y.shape[0], y.shape[2], y.shape[3]) if first else y.movedim(-1, 1)
         if first == 0 and self.fuse_head and o.is_cuda:
-            o = self._act(self._head_as_conv(o), k)
-            o = self.drop(o)
+            b, t = o.shape[0], o.shape[3]
+            kernel, _ = self._head_kernel(tuple(o.shape), dev, o.dtype, in_chain=False)
+            name = activations.serialize(d0.activation)
+            act = name if name in ('linear', 'relu') else 'linear'
+            y = Fq.quaternion_conv(o, kernel, d0.bias, 1, 'valid', 'channels_first', 1, act, conj=True)
+            if act != name:
+                y = d0.activation(y)
+            o = self.drop(self._act(y.reshape(b, d0.r.shape[-1], t).permute(0, 2, 1), k))     # (B, units, 1, T) -> (B, T, units)
             k, first = k + 1, 1
         elif first == 0:
             o = o.permute(0, 3, 1, 2)                        # Permute((3,1,2)): (B, T, C, F)
             o = o.reshape(o.shape[0], o.shape[1], o.shape[2] * o.shape[3])
+
+        # dense tail: the TimeDistributed(QuaternionDense(256)) layers not run yet (interspeech_model.py:150-166)
         for i in range(first, len(self.dense)):
-            o = self._act(self.dense[i](o), k)
-            k += 1
-            if i < 2:
-                o = self.drop(o)
-        return self._pred(o)
-
-    def _pred(self, o):
-        """The output layer on the (B, T, 256) features -- or the features themselves while ctc_mean_loss collects them for the fused
-        output-layer + cost node."""
-        if getattr(self, '_features_only', False):
-            return o
-        return self.pred(o)
-
-    def _first_layer_fused(self, x):
-        """conv (3,5) 'same' relu + MaxPooling2D((1,3), 'same') over the frequency axis (interspeech_model.py:97-103)
-        as ONE kernel per direction (functional.conv_relu_pool): the 41-bin activation is never written.  Returns None
-        when the configuration is outside that kernel (the layers then run one by one)."""
-        from .. import functional as Fq
-        from ..keras_like import activations
-        c, pl = self.conv, self.pool
-        if L.dbg(L.QK_DBG_NO_FUSED_FIRST) or not x.is_cuda or x.dim() != 4:
-            return None
-        if not c.built:
-            c._build_device = x.device
-            c.build(tuple(x.shape))
-        # a plain channels_first buffer (how the reference's callers hold the features) is read plane by plane by the
-        # kernel itself; a channels-last buffer behind a channels_first view (an upstream engine layer) is taken as it is
-        xl, lay = (x, 'channels_first') if x.is_contiguous() else (x.movedim(1, -1), 'channels_last')
-        kernel, bias = c.kernel, c.bias            # (any filter count that is a multiple of 8: start_filter = 16 runs the 32-filter blocks half used)
-        ok = (activations.serialize(c.activation) == 'relu' and c.padding == 'same' and c.strides == (1, 1) and
-              c.dilation_rate == (1, 1) and c.internal_layout == 'channels_last' and pl.pool_size == (1, 3) and
-              pl.strides == (1, 3) and pl.padding == 'same' and pl.data_format == 'channels_last' and
-              Fq.conv_relu_pool_supported(xl, kernel, 3, lay))
-        if not ok:
-            return None
-        y = Fq.conv_relu_pool(xl, kernel, bias, 3, lay)
-        return y.movedim(-1, 1)
-
-    def _forward_fused_post(self, x):
-        """The activation + Dropout behind every layer fused into the quaternion kernels.
-        aact == 'prelu' (interspeech_model.py:55-56,99-101,117-121: linear layers, PReLU(shared_axes=[1,0]) and Dropout
-        behind each): the producing kernel writes the pre-activation and the activated / dropped tensor, the next
-        layer's backward-data applies the derivative.
-        aact == 'none' with relu layers and an active Dropout (:117-121,131-137): the producing kernel writes ONLY
-        y = dropout(relu(pre)) and the next layer's backward-data multiplies its output by (y > 0) / (1 - rate) --
-        the same tensors and traffic as the dropout-free relu chain."""
-        from .. import functional as Fq
-        from ..keras_like import activations
-        self._new_drop_base()
-        c = self.conv
-        if not c.built:
-            c._build_device = x.device
-            c.build(tuple(x.shape))
-        shape = c.compute_output_shape(tuple(x.shape))
-        relu_form = self.prelu is None
-        post0 = self._post(0, shape, dropout=False)
-        pl = self.pool
-        xl, lay = (x, 'channels_first') if x.is_contiguous() else (x.movedim(1, -1), 'channels_last')   # see _first_layer_fused
-        o = self._first_layer_fused(x) if relu_form else None
-        fused_first = (not relu_form and
-                       not L.dbg(L.QK_DBG_NO_FUSED_FIRST) and x.dim() == 4 and c.padding == 'same' and c.strides == (1, 1) and
-                       c.dilation_rate == (1, 1) and c.internal_layout == 'channels_last' and pl.pool_size == (1, 3) and
-                       pl.strides == (1, 3) and pl.padding == 'same' and pl.data_format == 'channels_last' and
-                       Fq.conv_prelu_pool_supported(xl, c.kernel, post0['alpha'], post0['alpha_axis'], 3, lay))
-        if o is not None:
-            pass             # conv + relu + frequency pooling ran as one kernel per direction (qk_conv_relu_pool_*)
-        elif relu_form:
-            o = self.pool(c(x))
-        elif fused_first:    # linear conv + PReLU + frequency pooling as ONE kernel per direction (qk_conv_prelu_pool_*)
-            o = Fq.conv_prelu_pool(xl, c.kernel, c.bias, post0['alpha'], post0['alpha_axis'], 3, lay).movedim(-1, 1)
-        else:
-            o = Fq.quaternion_conv(x, c.kernel, c.bias, strides=c.strides, padding=c.padding, data_format='channels_first',
-                                   dilation_rate=c.dilation_rate, activation=None, post=post0)
-            o = self.pool(o)
-        shape = tuple(o.shape)
-        layers = []
-        for i, cv in enumerate(self.convs):
-            if not cv.built:
-                cv._build_device = x.device
-                cv.build(shape)
-            shape = cv.compute_output_shape(shape)
-            layers.append((cv.kernel, cv.bias, dict(strides=cv.strides, padding=cv.padding, dilation_rate=cv.dilation_rate,
-                                                    activation=None, post=self._post(1 + i, shape))))
-        k = 1 + len(self.convs)
-        d0 = self.dense[0].layer
-        if not d0.built:
-            d0._build_device = x.device
-            d0.build((None, shape[1] * shape[2]))
-        dl, link = self._head_link(shape, x.device, o.dtype, activation=None, post=self._post(k, (shape[0], shape[3], d0.r.shape[-1])))
-        head_shape = (shape[0], dl.r.shape[-1], shape[3])                       # (B, units, T): TimeDistributed output, channels_first view
-        layers.append(link)
-        k += 1
-        if relu_form and not L.dbg(L.QK_DBG_NO_DENSE_IN_CHAIN):
-            # aact == 'none': the second and third TimeDistributed(QuaternionDense(256)) (interspeech_model.py:150-166) are links
-            # of the SAME chain -- 1 x 1 conj-convolutions on the (B, 1, T, 256) tensor, relu (+ dropout behind the second) as the
-            # producing kernel's post-op, its derivative in the consumer's backward-data epilogue: no separate activation /
-            # dropout pass in either direction
-            width = head_shape[1]
-            for i in (1, 2):
-                dn = self.dense[i].layer
-                if not dn.built:
-                    dn._build_device = x.device
-                    dn.build((None, width))
-                width = dn.r.shape[-1]
-                layers.append((dn.r, dn.bias, dict(activation=None, post=self._post(k, (shape[0], shape[3], width), dropout=(i < 2)))))
-                k += 1
-            y = Fq.quaternion_conv_chain(o.movedim(1, -1), layers)              # (B, 1, T, units)
-            return self._pred(y.reshape(y.shape[0], y.shape[2], y.shape[3]))
-        y = Fq.quaternion_conv_chain(o.movedim(1, -1), layers)                  # (B, 1, T, units)
-        o = y.reshape(y.shape[0], y.shape[2], y.shape[3])
-        for i in (1, 2):
-            dn = self.dense[i].layer
-            b, t = o.shape[0], o.shape[1]
-            if not dn.built:
-                dn._build_device = x.device
-                dn.build((None, o.shape[2]))
-            po = self._post(k, (b, t, dn.r.shape[-1]), dropout=(i < 2))
-            if relu_form and po['rate'] == 0.0:
-                o = Fq.quaternion_dense(o.reshape(b * t, o.shape[2]), dn.r, dn.bias, activation='relu').reshape(b, t, -1)
+            if fused:                                        # the slot's post-op as its own pass (relu alone: the GEMM epilogue)
+                dn, (b, t, w) = self.dense[i].layer, o.shape
+                dn.ensure_built((None, w), dev)
+                po = self._post(k, (b, t, dn.r.shape[-1]), dev, dropout=(i < 2))
+                relu = relu_form and po['rate'] == 0.0
+                o = Fq.quaternion_dense(o.reshape(b * t, w), dn.r, dn.bias, activation='relu' if relu else None).reshape(b, t, -1)
+                if not relu:
+                    o = Fq.prelu_dropout(o, po['alpha'], po['alpha_axis'], po['rate'], po['seed'])
             else:
-                h = Fq.quaternion_dense(o.reshape(b * t, o.shape[2]), dn.r, dn.bias, activation=None).reshape(b, t, -1)
-                o = Fq.prelu_dropout(h, po['alpha'], po['alpha_axis'], po['rate'], po['seed'])
+                o = self._act(self.dense[i](o), k)
+                if i < 2:
+                    o = self.drop(o)
             k += 1
-        return self._pred(o)
-
-    def _head_kernel(self, o_shape, device):
-        """The first dense layer's weight r[(cq*F + f), :] viewed as the (F, 1, Cq, units) kernel of the
-        equivalent 'valid' conj-convolution over (F, T) (see _head_as_conv)."""
-        dl = self.dense[0].layer
-        b, c, f, t = o_shape
-        if not dl.built:
-            dl._build_device = device
-            dl.build((None, c * f))
-        return dl, dl.r.view(c // 4, f, dl.r.shape[-1]).permute(1, 0, 2).unsqueeze(1).contiguous()
-
-    def _head_link(self, o_shape, device, dtype, **kw):
-        """The head as a chain link (kernel, bias, kwargs).  16-bit device tensors with matrix-core widths: the dense PARAMETER
-        itself, read in place as a channel-major kernel (functional.quaternion_conv_chain: dense_kernel_size) -- the permuted
-        copy of `_head_kernel`, its re-layout launches and the permuted gradient accumulation (8 small launches per step)
-        go away; anything else: the (F, 1, Cq, units) copy."""
-        dl, w = None, None
-        b, c, f, t = o_shape
-        d0 = self.dense[0].layer
-        if not d0.built:
-            d0._build_device = device
-            d0.build((None, c * f))
-        cq, fq = c // 4, d0.r.shape[-1] // 4
-        if (dtype in (torch.bfloat16, torch.float16) and str(device).startswith('cuda') and cq % 32 == 0 and fq % 32 == 0
-                and d0.r.is_contiguous()):
-            return d0, (d0.r, d0.bias, dict(kw, conj=True, dense_kernel_size=(f, 1)))
-        dl, w = self._head_kernel(o_shape, device)
-        return dl, (w, dl.bias, dict(kw, strides=1, padding='valid', dilation_rate=1, conj=True))
-
-    def _convs_as_chain(self, o):
-        """The n body convolutions (interspeech_model.py:105-137 with no advanced activation and no active
-        dropout) through functional.quaternion_conv_chain: same values and gradients as calling the layers
-        one by one, but each relu derivative is applied where it is cheapest.
-        With fuse_head the first TimeDistributed dense layer (as an (F, 1) convolution) is the last link
-        of the chain, so the last body convolution's relu derivative also moves into a backward-data
-        epilogue.  Returns (tensor, head_included)."""
-        from .. import functional as Fq
-        from ..keras_like import activations
-        shape = tuple(o.shape)
-        layers = []
-        for c in self.convs:
-            if not c.built:
-                c._build_device = o.device
-                c.build(shape)
-            shape = c.compute_output_shape(shape)
-            name = activations.serialize(c.activation)
-            if name not in ('linear', 'relu'):
-                return self._convs_one_by_one(o), False
-            layers.append((c.kernel, c.bias, dict(strides=c.strides, padding=c.padding,
-                                                  dilation_rate=c.dilation_rate, activation=name)))
-        with_head = False
-        if self.fuse_head:
-            name = activations.serialize(self.dense[0].layer.activation)
-            if name in ('linear', 'relu'):
-                dl, link = self._head_link(shape, o.device, o.dtype, activation=name)
-                layers.append(link)
-                with_head = True
-        y = Fq.quaternion_conv_chain(o.movedim(1, -1), layers)       # (B, F, T, C) channels-last buffer
-        if with_head:
-            return y.reshape(y.shape[0], y.shape[2], y.shape[3]), True   # (B, 1, T, units) -> (B, T, units)
-        return y.movedim(-1, 1), False
-
-    def _convs_one_by_one(self, o):
-        for c in self.convs:
-            o = c(o)
         return o
-
-    def _head_as_conv(self, o):
-        """Permute((3,1,2)) + reshape + TimeDistributed(QuaternionDense) (interspeech_model.py:141-149) on
-        the conv output (B, C, F, T) WITHOUT the 367 MB transpose copy: feature c*F + f of time step t
-        is o[b, c, f, t], so the dense layer is a quaternion convolution with an (F, 1) 'valid' kernel
-        over (F, T) -- same GEMM (K = F*C), same conj(W) (x) x table -- whose kernel is the dense weight
-        r[(cq*F + f), :] re-indexed to [f, 0, cq, :].  Parameters stay the reference's (in_q, units)."""
-        from .. import functional as Fq
-        from ..keras_like import activations
-        b, c, f, t = o.shape
-        dl, w = self._head_kernel(tuple(o.shape), o.device)
-        name = activations.serialize(dl.activation)
-        fused = name if name in ('linear', 'relu') else 'linear'
-        y = Fq.quaternion_conv(o, w, dl.bias, 1, 'valid', 'channels_first', 1, fused, conj=True)
-        if fused != name:
-            y = dl.activation(y)
-        return y.reshape(b, dl.r.shape[-1], t).permute(0, 2, 1)                      # (B, units, 1, T) -> (B, T, units)
 
     def ctc_loss(self, x, labels, input_length, label_length, loss_scale=1.0):
         """The model output of the reference: K.ctc_batch_cost per sample, shape (B, 1) (interspeech_model.py:178).
@@ -340,22 +242,15 @@ class TimitQCNN(torch.nn.Module):
         `loss={'ctc': lambda y_true, y_pred: y_pred}`, i.e. the mean of the per-sample costs of interspeech_model.py:178).  Same value
         and gradients as `self.ctc_loss(...).mean()`; on the device the output layer, the CTC cost and the mean are ONE autograd node
         (layers.dense_softmax_ctc_mean: no framework launch between the CTC kernel and the output layer's backward)."""
-        from ..layers import dense_softmax_ctc_mean
+        if not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16)):
+            return self.ctc_loss(x, labels, input_length, label_length, loss_scale=loss_scale).mean()
+        feats = self.features(x)
         dense = self.pred.layer
-        if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and hasattr(self, '_pred'):
-            self._features_only = True
-            try:
-                feats = self(x)
-            finally:
-                self._features_only = False
-            if not dense.built:
-                dense._build_device = x.device
-                dense.build((None, feats.shape[-1]))
-            loss = dense_softmax_ctc_mean(feats, dense, labels, input_length, label_length, loss_scale) if feats.dim() == 3 else None
-            if loss is not None:
-                return loss
-            return ctc_batch_cost(self.pred(feats), labels, input_length, label_length, loss_scale=loss_scale).mean()
-        return self.ctc_loss(x, labels, input_length, label_length, loss_scale=loss_scale).mean()
+        dense.ensure_built((None, feats.shape[-1]), x.device)
+        loss = dense_softmax_ctc_mean(feats, dense, labels, input_length, label_length, loss_scale)
+        if loss is None:
+            loss = ctc_batch_cost(self.pred(feats), labels, input_length, label_length, loss_scale=loss_scale).mean()
+        return loss
 
     # ---- validation: decoding and phone error rate ------------------------------------------------------------------------------
     def _inference(self, fn):
@@ -407,12 +302,7 @@ class TimitQCNN(torch.nn.Module):
             raise ValueError('evaluate: a language model needs the beam search (greedy=False)')
 
         def run():
-            self._features_only = True
-            try:
-                feats = self(x)
-            finally:
-                self._features_only = False
-            y = self.pred(feats)
+            y = self(x)
             loss = ctc_batch_cost(y, labels, input_length, label_length).mean()
             decoded, log_prob = ctc_decode(y, input_length, greedy=greedy, beam_width=beam_width, top_paths=1, lm=lm,
                                            lm_weight=lm_weight, insertion_bonus=insertion_bonus)
@@ -509,8 +399,11 @@ class TimitRealCNN(torch.nn.Module):
                 o = self.drop(o)
         return self.pred(o)
 
+    def ctc_mean_loss(self, x, labels, input_length, label_length, loss_scale=1.0):
+        """mean over the batch of ctc_loss(...): the composed output layer, CTC cost and mean (no fused node here)."""
+        return self.ctc_loss(x, labels, input_length, label_length, loss_scale=loss_scale).mean()
+
     ctc_loss = TimitQCNN.ctc_loss
-    ctc_mean_loss = TimitQCNN.ctc_mean_loss
     regularization_loss = TimitQCNN.regularization_loss
     training_loss = TimitQCNN.training_loss
 

@@ -70,6 +70,19 @@ def test_cpu_tensors_raise_instead_of_falling_back():
         QuaternionDense(8)(torch.randn(3, 8))
 
 
+def test_fused_output_layer_ctc_node_rejects_a_bad_loss_scale_like_ctc_batch_cost():
+    """layers.dense_softmax_ctc_mean validates loss_scale as functional.ctc_batch_cost does (positive, finite), before it
+    decides whether its fused node takes the shapes -- host tensors, which it leaves to the caller's composition, included."""
+    from qcnn_amd.layers import Dense, dense_softmax_ctc_mean
+    dense = Dense(62, activation='softmax')
+    dense.ensure_built((None, 16), torch.device('cpu'))
+    feats, labels, lengths = torch.randn(2, 10, 16), torch.zeros(2, 3, dtype=torch.int32), torch.full((2, 1), 3, dtype=torch.int32)
+    for bad in (0.0, -1.0, float('inf'), float('nan')):
+        with pytest.raises(ValueError, match='loss_scale'):
+            dense_softmax_ctc_mean(feats, dense, labels, lengths, lengths, loss_scale=bad)
+    assert dense_softmax_ctc_mean(feats, dense, labels, lengths, lengths, loss_scale=4096.0) is None
+
+
 def test_product_package_never_imports_the_oracle():
     import glob
     pkg = os.path.dirname(qcnn_amd.__file__)

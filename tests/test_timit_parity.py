@@ -175,7 +175,8 @@ def test_timit_qcnn_relu_dropout_matches_oracle_composition(dtype):
         (pred.double() * torch.tensor(dpred, device=dev)).sum().backward()
         return pred
     pred, forced = _capture_layer_outputs(model, xt, run)
-    # the masks of this forward pass: seed of the k-th activation slot = base + 7919 k (TimitQCNN._post)
+    # the masks of this forward pass: activation slot k has seed base + 7919 (k + 1) (TimitQCNN._post), so conv i (slot 1 + i)
+    # has seed(2 + i) below
     base, n = model._drop_base, len(model.convs)
     seed = lambda k: (base + 7919 * k) & 0xffffffff
     keeps = {}
