@@ -10,6 +10,10 @@ time derivatives as the quaternion components), computed on the device per batch
 the loss is TimitQCNN.training_loss (mean CTC cost + the l2 terms) with the fused Adam kernel; every --eval-every steps the held-out
 CTC cost and the 39-class phone error rate (Lee & Hon folding) of one held-out batch are printed.
 
+--clipnorm / --clipvalue (Keras' Adam(clipnorm=, clipvalue=)), --dtype float16 and --dynamic-loss-scale switch the optimiser step to
+qcnn_amd.training.GradGuard: gradient norm, overflow check, clipping and the loss-scale update run on the device, a step with an inf /
+NaN gradient is skipped, and every log line shows the norm, the scale and the number of skipped steps.
+
 --lm-order N (1-3; 0 = off) estimates an interpolated Kneser-Ney phone N-gram LM (qcnn_amd.lm.NgramLM) from the TRAIN transcripts,
 prints its held-out perplexity, and adds to every evaluation the PER(39) of the beam search (--beam-width) without and with the LM
 fused in (--lm-weight, --insertion-bonus).
@@ -31,6 +35,7 @@ from qcnn_amd.data import TIMIT_PHONES_61, read_audio, read_phn, timit_61_to_39_
 from qcnn_amd.features import quaternion_fbank  # noqa: E402
 from qcnn_amd.lm import NgramLM  # noqa: E402
 from qcnn_amd.models import getTimitModel2D  # noqa: E402
+from qcnn_amd.training import GradGuard  # noqa: E402
 
 
 def load_split(root):
@@ -95,10 +100,15 @@ def main():
     ap.add_argument('--lm-weight', type=float, default=0.5)
     ap.add_argument('--insertion-bonus', type=float, default=0.0)
     ap.add_argument('--beam-width', type=int, default=16, help='beam width of the LM comparison')
+    ap.add_argument('--clipnorm', type=float, default=0.0, help='global gradient-norm clip, as Adam(clipnorm=) in Keras (0: off)')
+    ap.add_argument('--clipvalue', type=float, default=0.0, help='element-wise gradient clamp behind it, as Adam(clipvalue=) (0: off)')
+    ap.add_argument('--dtype', default='bfloat16', choices=['bfloat16', 'float16'], help='activation dtype')
+    ap.add_argument('--dynamic-loss-scale', action='store_true',
+                    help='loss scale on the device, starting at 2^12: halved on an overflowing (skipped) step, doubled after 2000 good ones')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
-    dtype = torch.bfloat16
+    dtype = getattr(torch, args.dtype)
 
     train = load_split(find_split(args.timit, 'TRAIN'))
     test = load_split(find_split(args.timit, 'TEST'))
@@ -127,13 +137,30 @@ def main():
     flat = dp.FlatParams([p for p in model.parameters() if p.requires_grad])   # the l2 terms come through training_loss
     m, v = torch.zeros_like(flat.param), torch.zeros_like(flat.param)
     rng = np.random.RandomState(args.seed)
+    # clipping / float16 / dynamic scaling: the guarded step (qcnn_amd.training.GradGuard).  Norm, overflow check, clip and scale
+    # update all happen on the device, and so does the step count (a skipped step does not advance it).
+    guard = None
+    if args.clipnorm > 0 or args.clipvalue > 0 or args.dynamic_loss_scale or dtype == torch.float16:
+        guard = GradGuard(dev, clipnorm=args.clipnorm, clipvalue=args.clipvalue, dynamic=args.dynamic_loss_scale,
+                          loss_scale=2.0 ** 12 if dtype == torch.float16 or args.dynamic_loss_scale else 1.0)
+        step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
     for step in range(1, args.steps + 1):
         x, il, labels, ll = to_device(train, batches[rng.randint(len(batches))], dev, dtype)
-        loss = model.training_loss(x, labels, il, ll)
-        loss.backward()
-        F.adam_step(flat.param, flat.grad, m, v, step, lr=args.lr, zero_grad=True)
+        if guard is None:
+            loss = model.training_loss(x, labels, il, ll)
+            loss.backward()
+            F.adam_step(flat.param, flat.grad, m, v, step, lr=args.lr, zero_grad=True)
+        else:
+            loss = model.training_loss(x, labels, il, ll, loss_scale=guard.loss_scale)
+            loss.backward()
+            guard.step(flat.param, flat.grad, m, v, step_dev, lr=args.lr, zero_grad=True)
         if step == 1 or step % 50 == 0 or step == args.steps:
-            print('step %5d  loss %.4f' % (step, float(loss)))
+            if guard is None:
+                print('step %5d  loss %.4f' % (step, float(loss)))
+            else:
+                s = guard.stats()                                     # (the one host read of the guard, at log lines only)
+                print('step %5d  loss %.4f  grad norm %.4g  loss scale %g  skipped %d'
+                      % (step, float(loss), s['last_norm'], s['scale'], s['skipped_steps']))
         if args.eval_every > 0 and step % args.eval_every == 0 and held_out is not None:
             xe, ile, le, lle = to_device(test, held_out, dev, dtype)
             res = model.evaluate(xe, le, ile, lle, class_map=class_map)

@@ -565,6 +565,72 @@ int qk_adam_step_dev(float *param, float *grad, float *m, float *v, const float 
                      float beta1, float beta2, float eps, int32_t *step_dev, float grad_scale, int32_t zero_grad,
                      void *stream);
 
+/* ---- Guarded optimiser step: gradient clipping and dynamic loss scaling, entirely on the device ------------------------------
+ * Two calls per training step on the flat fp32 buffers of qk_adam_step_dev:
+ *
+ *   qk_grad_guard_reduce   one deterministic reduction over the gradient buffer: global l2 norm and the number of non-finite
+ *                          elements, then the decisions of the step, written into a 32-byte DEVICE state block;
+ *   qk_adam_step_guarded   qk_adam_step_dev that reads those decisions from the block.
+ *
+ * No launch argument depends on data and nothing is read on the host, so the pair is captured into a graph with the rest of the
+ * training step; the reduction uses no atomics and a grid that depends on n alone, so its result is bit-repeatable and ranks
+ * that reduced the same (all-reduced) buffer take the same decision.
+ *
+ * Mirrors keras.optimizers.Adam(clipnorm=, clipvalue=) of Keras 2 (Optimizer.get_gradients): clipnorm is the GLOBAL clip --
+ * every gradient is multiplied by clipnorm / norm when the l2 norm over ALL of them exceeds clipnorm -- and clipvalue clamps each
+ * element to [-clipvalue, clipvalue] AFTER that.  The gradient the norm is taken of is the one Adam consumes,
+ * g_i = grad_i * unscale (+ decay_i * param_i), i.e. including the l2 regularisers' term, as in Keras where that term is part of
+ * the loss.  ONE deviation from Keras: a step whose gradient holds an inf or a NaN is SKIPPED (param, m, v and the step counter
+ * stay as they are), and with `dynamic` set the loss scale backs off on such a step and grows after growth_interval applied steps
+ * in a row -- dynamic loss scaling for float16 training; Keras 2 has neither the skip nor the scale. */
+typedef struct qk_grad_guard_config_t {
+    float clipnorm;          /* > 0: global-norm clip; 0: off */
+    float clipvalue;         /* > 0: element clamp behind the norm clip; 0: off */
+    int32_t dynamic;         /* != 0: qk_grad_guard_reduce updates state.scale (below) */
+    float growth_factor;     /* > 1 */
+    float backoff_factor;    /* in (0, 1) */
+    int32_t growth_interval; /* >= 1 */
+    float min_scale;         /* 0 < min_scale <= max_scale */
+    float max_scale;
+} qk_grad_guard_config_t;
+
+/* The state block, in DEVICE memory (32 bytes, 4-byte aligned; the caller initialises scale, good_steps and skipped_steps --
+ * scale to the loss scale the backward was run with, 1 without loss scaling -- and may read it back at any time).  `scale` is
+ * the value the NEXT backward has to multiply its gradient by: hand a pointer to it to whatever forms the loss gradient. */
+typedef struct qk_grad_guard_state_t {
+    float scale;             /* current loss scale (updated by qk_grad_guard_reduce when config.dynamic) */
+    int32_t good_steps;      /* applied steps since the scale last changed (dynamic only) */
+    int32_t skipped_steps;   /* steps skipped so far (dynamic only) */
+    int32_t last_skipped;    /* 1: the step just reduced holds a non-finite gradient and is not applied */
+    float last_norm;         /* its l2 norm; +inf when nonfinite_count > 0 (or when the norm exceeds fp32) */
+    float last_coef;         /* (clipnorm > 0 && norm > clipnorm) ? clipnorm / norm : 1 */
+    float last_unscale;      /* grad_scale / scale with the scale the step was RUN with (before the update) */
+    int32_t nonfinite_count; /* inf / NaN elements among the g_i (saturates at INT32_MAX) */
+} qk_grad_guard_state_t;
+
+/* Bytes of workspace qk_grad_guard_reduce needs for n elements (host only; positive, non-decreasing in n). */
+size_t qk_grad_guard_workspace_bytes(size_t n);
+
+/* norm = sqrt(sum g_i^2), g_i = grad_i * unscale (+ decay_i * param_i) formed in fp32 with unscale = grad_scale / state->scale
+ * (fp32), the squares summed in fp64 (gradients of 1e25 do not overflow the sum); non-finite g_i are counted on the elements.
+ * Stage one writes one partial per workgroup into `workspace` (grid-stride, grid capped and a function of n only), stage two --
+ * one workgroup -- adds them in index order and then writes last_norm, nonfinite_count, last_skipped, last_coef and last_unscale
+ * and, with config->dynamic: skipped step: scale = max(scale * backoff_factor, min_scale), good_steps = 0, skipped_steps += 1;
+ * applied step: good_steps += 1 and at growth_interval scale = min(scale * growth_factor, max_scale), good_steps = 0.
+ * param and decay are both NULL or both given.  grad (and param, decay) need 4-byte alignment only: views at any element offset
+ * of a flat buffer are read with 16-byte loads behind a peeled head.  workspace: 16-byte aligned. */
+int qk_grad_guard_reduce(const float *grad, const float *param, const float *decay, size_t n, float grad_scale,
+                         const qk_grad_guard_config_t *config, qk_grad_guard_state_t *state, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
+/* qk_adam_step_dev on  g = (grad * state->last_unscale (+ decay * param)) * state->last_coef, clamped to +-config->clipvalue when
+ * that is > 0.  With state->last_skipped set, param, m, v and *step_dev are left as they are; grad is still cleared when
+ * zero_grad != 0 (the inf would otherwise stay in an accumulating buffer).  With clipping off, scale 1 and a finite gradient the
+ * results are bit-identical to qk_adam_step_dev's.  Run it behind qk_grad_guard_reduce on the same stream. */
+int qk_adam_step_guarded(float *param, float *grad, float *m, float *v, const float *decay, size_t n, float lr,
+                         float beta1, float beta2, float eps, int32_t *step_dev, int32_t zero_grad,
+                         const qk_grad_guard_config_t *config, const qk_grad_guard_state_t *state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,18 @@ class ProfRec(ctypes.Structure):
                 ('ms', ctypes.c_float)]
 
 
+class GradGuardConfig(ctypes.Structure):
+    """qk_grad_guard_config_t (include/qk.h)"""
+    _fields_ = [('clipnorm', ctypes.c_float), ('clipvalue', ctypes.c_float), ('dynamic', I32),
+                ('growth_factor', ctypes.c_float), ('backoff_factor', ctypes.c_float), ('growth_interval', I32),
+                ('min_scale', ctypes.c_float), ('max_scale', ctypes.c_float)]
+
+
+# qk_grad_guard_state_t: eight 4-byte fields in device memory; (name, is_float) in order
+GRAD_GUARD_STATE = (('scale', True), ('good_steps', False), ('skipped_steps', False), ('last_skipped', False),
+                    ('last_norm', True), ('last_coef', True), ('last_unscale', True), ('nonfinite_count', False))
+_GC = ctypes.POINTER(GradGuardConfig)
+
 SYMBOLS = {
     'qk_version': (ctypes.c_int, []),
     'qk_prof_enable': (ctypes.c_int, [ctypes.c_int]),
@@ -140,6 +152,10 @@ SYMBOLS = {
     'qk_maxpool2d_bwd': (ctypes.c_int, [_PD, _VP, _VP, _VP, _VP]),
     'qk_adam_step': (ctypes.c_int, [_FP, _FP, _FP, _FP, _SZ, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, I32, ctypes.c_float, _VP]),
+    'qk_grad_guard_workspace_bytes': (_SZ, [_SZ]),
+    'qk_grad_guard_reduce': (ctypes.c_int, [_FP, _FP, _FP, _SZ, ctypes.c_float, _GC, _VP, _VP, _SZ, _VP]),
+    'qk_adam_step_guarded': (ctypes.c_int, [_FP, _FP, _FP, _FP, _FP, _SZ, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                            ctypes.c_float, _VP, I32, _GC, _VP, _VP]),
 }
 
 _lib = None

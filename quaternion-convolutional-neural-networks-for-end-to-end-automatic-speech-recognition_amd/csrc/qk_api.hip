@@ -1355,4 +1355,49 @@ int qk_adam_step_dev(float *param, float *grad, float *m, float *v, const float 
     return check_launch(launch_adam(param, grad, m, v, decay, n, lr, beta1, beta2, eps, 1, grad_scale, zero_grad != 0, (hipStream_t)stream, step_dev), "qk_adam_step_dev");
 }
 
+static bool guard_config_ok(const qk_grad_guard_config_t *c, const char *what)
+{
+    if (!c) { set_error("%s: NULL config", what); return false; }
+    if (!(c->clipnorm >= 0.f) || !(c->clipvalue >= 0.f)) { set_error("%s: clipnorm / clipvalue must be >= 0", what); return false; }
+    if (c->dynamic && !(c->backoff_factor > 0.f && c->backoff_factor < 1.f && c->growth_factor > 1.f && c->growth_interval >= 1
+                        && c->min_scale > 0.f && c->min_scale <= c->max_scale)) {
+        set_error("%s: dynamic scaling needs 0 < backoff_factor < 1 < growth_factor, growth_interval >= 1, 0 < min_scale <= max_scale", what);
+        return false;
+    }
+    return true;
+}
+
+size_t qk_grad_guard_workspace_bytes(size_t n) { return grad_guard_workspace_bytes(n); }
+
+int qk_grad_guard_reduce(const float *grad, const float *param, const float *decay, size_t n, float grad_scale,
+                         const qk_grad_guard_config_t *config, qk_grad_guard_state_t *state, void *workspace,
+                         size_t workspace_bytes, void *stream)
+{
+    if (!grad || !state || !workspace) { set_error("qk_grad_guard_reduce: NULL grad, state or workspace"); return QK_ERR_INVALID_ARG; }
+    if (n == 0) { set_error("qk_grad_guard_reduce: n must be > 0"); return QK_ERR_INVALID_ARG; }
+    if ((param == nullptr) != (decay == nullptr)) { set_error("qk_grad_guard_reduce: param and decay go together"); return QK_ERR_INVALID_ARG; }
+    if (!guard_config_ok(config, "qk_grad_guard_reduce")) return QK_ERR_INVALID_ARG;
+    if (!aligned(grad, 4) || !aligned(state, 4) || (param && (!aligned(param, 4) || !aligned(decay, 4))) || !aligned(workspace, 16)) {
+        set_error("qk_grad_guard_reduce: buffers need 4-byte alignment, the workspace 16-byte alignment");
+        return QK_ERR_INVALID_ARG;
+    }
+    if (workspace_bytes < grad_guard_workspace_bytes(n)) {
+        set_error("qk_grad_guard_reduce: workspace of %zu bytes, %zu needed", workspace_bytes, grad_guard_workspace_bytes(n));
+        return QK_ERR_INVALID_ARG;
+    }
+    return check_launch(launch_grad_guard_reduce(grad, param, decay, n, grad_scale, *config, state, workspace, (hipStream_t)stream),
+                        "qk_grad_guard_reduce");
+}
+
+int qk_adam_step_guarded(float *param, float *grad, float *m, float *v, const float *decay, size_t n, float lr, float beta1,
+                         float beta2, float eps, int32_t *step_dev, int32_t zero_grad, const qk_grad_guard_config_t *config,
+                         const qk_grad_guard_state_t *state, void *stream)
+{
+    if (!param || !grad || !m || !v || !step_dev || !state) { set_error("qk_adam_step_guarded: NULL buffer, step counter or state"); return QK_ERR_INVALID_ARG; }
+    if (n == 0) { set_error("qk_adam_step_guarded: n must be > 0"); return QK_ERR_INVALID_ARG; }
+    if (!guard_config_ok(config, "qk_adam_step_guarded")) return QK_ERR_INVALID_ARG;
+    return check_launch(launch_adam_guarded(param, grad, m, v, decay, n, lr, beta1, beta2, eps, step_dev, zero_grad != 0, config->clipvalue,
+                                            state, (hipStream_t)stream), "qk_adam_step_guarded");
+}
+
 }  // extern "C"

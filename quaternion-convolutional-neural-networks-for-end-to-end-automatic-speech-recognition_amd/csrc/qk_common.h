@@ -388,6 +388,12 @@ int launch_dense_softmax_bwd(int dtype, long long rows, int K, int U, const void
                              float *dw, float *dbias, const float *dy_scale_dev, float dy_scale, float *ws, hipStream_t stream);
 int launch_adam(float *p, float *g, float *m, float *v, const float *decay, size_t n, float lr, float b1,
                 float b2, float eps, int step, float gscale, bool zero_grad, hipStream_t stream, int *step_dev = nullptr);
+// guarded optimiser step (qk_train.hip)
+size_t grad_guard_workspace_bytes(size_t n);
+int launch_grad_guard_reduce(const float *grad, const float *param, const float *decay, size_t n, float grad_scale,
+                             const qk_grad_guard_config_t &cfg, qk_grad_guard_state_t *state, void *ws, hipStream_t stream);
+int launch_adam_guarded(float *p, float *g, float *m, float *v, const float *decay, size_t n, float lr, float b1, float b2, float eps,
+                        int *step_dev, bool zero_grad, float clipvalue, const qk_grad_guard_state_t *state, hipStream_t stream);
 
 void set_error(const char *fmt, ...);
 void note_path(int qk_path);          // thread-local record behind qk_last_path()

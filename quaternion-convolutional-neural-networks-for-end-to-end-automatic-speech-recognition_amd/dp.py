@@ -12,6 +12,10 @@ step is ONE sum all-reduce of the flat fp32 compact-gradient buffer:
     and for these <= 150 MB buffers latency, not bandwidth, is what matters -> one big
     message, not per-layer messages);
   * the 1/world_size averaging is folded into the fused Adam kernel (`grad_scale`);
+  * gradient clipping / dynamic loss scaling (`training.GradGuard`) need no exchange of their own: every rank runs the guard
+    on its own copy of the all-reduced buffer with `grad_scale = 1 / world_size`; the norm reduction is deterministic (fixed
+    grid, fixed order, no atomics), so identical buffers give identical norms and every rank takes the same skip / clip /
+    scale decision;
   * `torch.distributed` backend "nccl" IS RCCL on ROCm; "gloo" is used by the CPU tests.
 """
 import os

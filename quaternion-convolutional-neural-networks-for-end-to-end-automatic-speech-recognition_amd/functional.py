@@ -683,6 +683,74 @@ def adam_step(param, grad, m, v, step, lr=0.001, beta1=0.9, beta2=0.999, eps=1e-
         refresh_prepped_kernels(param)
 
 
+def _flat_f32(what, *tensors):
+    for t in tensors:
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise RuntimeError('%s needs contiguous float32 device buffers' % what)
+
+
+def _guard_state_ok(what, state, device):
+    if (not isinstance(state, torch.Tensor) or state.dtype != torch.float32 or state.numel() != len(L.GRAD_GUARD_STATE)
+            or not state.is_contiguous() or state.device != device):
+        raise TypeError('%s: state must be the %d-element float32 device block of qk_grad_guard_state_t on the buffers\' device'
+                        % (what, len(L.GRAD_GUARD_STATE)))
+
+
+def grad_guard_reduce(grad, config, state, param=None, decay=None, grad_scale=1.0, workspace=None):
+    """qk_grad_guard_reduce: the deterministic norm / non-finite reduction of the flat gradient and the step's decisions, written
+    into `state` (the 8-element float32 device block that holds qk_grad_guard_state_t; training.GradGuard owns one).  config: a
+    _lib.GradGuardConfig.  Nothing is read on the host."""
+    _flat_f32('grad_guard_reduce', grad, param, decay)
+    _guard_state_ok('grad_guard_reduce', state, grad.device)
+    if (param is None) != (decay is None):
+        raise ValueError('grad_guard_reduce: param and decay go together')
+    n = grad.numel()
+    if decay is not None and (decay.numel() != n or param.numel() != n):
+        raise ValueError('param and decay must have one element per gradient element')
+    need = int(L.lib().qk_grad_guard_workspace_bytes(n))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=grad.device)
+    with _on_device(grad.device):
+        rc = L.lib().qk_grad_guard_reduce(_ptr(grad), _ptr(param), _ptr(decay), n, grad_scale, ctypes.byref(config), _ptr(state),
+                                          _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(grad))
+    L.check(rc, 'qk_grad_guard_reduce')
+
+
+def grad_norm(grad, param=None, decay=None, grad_scale=1.0):
+    """(norm, nonfinite_count) of the flat float32 gradient as one-element DEVICE tensors (float32, int32): the global l2 norm of
+    g = grad * grad_scale (+ decay * param), squares summed in float64 in a fixed order (bit-repeatable, no atomics), and the
+    number of inf / NaN elements; the norm is +inf when there are any.  Two launches, no host read (qk_grad_guard_reduce with an
+    inert configuration)."""
+    _flat_f32('grad_norm', grad)
+    state = torch.zeros(len(L.GRAD_GUARD_STATE), dtype=torch.float32, device=grad.device)
+    state[0] = 1.0
+    grad_guard_reduce(grad, L.GradGuardConfig(), state, param, decay, grad_scale)
+    return state[4:5], state.view(torch.int32)[7:8]
+
+
+def adam_step_guarded(param, grad, m, v, step, config, state, lr=0.001, beta1=0.9, beta2=0.999, eps=1e-7, zero_grad=False,
+                      decay=None):
+    """adam_step(step=<device tensor>) on the gradient grad_guard_reduce decided on (qk_adam_step_guarded): unscaled by
+    state.last_unscale, clipped by state.last_coef and config.clipvalue, and not applied at all -- param, m, v and the step
+    counter untouched, grad still cleared under zero_grad -- when state.last_skipped is set.  Run it behind grad_guard_reduce on
+    the same buffers; training.GradGuard.step does both."""
+    _flat_f32('adam_step_guarded', param, grad, m, v, decay)
+    _guard_state_ok('adam_step_guarded', state, param.device)
+    if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or not step.is_cuda or step.numel() != 1:
+        raise TypeError('adam_step_guarded: the step counter must be a one-element int32 device tensor (a skipped step makes '
+                        'the count data-dependent)')
+    n = param.numel()
+    if decay is not None and decay.numel() != n:
+        raise ValueError('decay must have one coefficient per parameter element')
+    with _on_device(param.device):
+        rc = L.lib().qk_adam_step_guarded(_ptr(param), _ptr(grad), _ptr(m), _ptr(v), _ptr(decay), n, lr, beta1, beta2, eps,
+                                          _ptr(step), int(bool(zero_grad)), ctypes.byref(config), _ptr(state), _stream(param))
+    L.check(rc, 'qk_adam_step_guarded')
+    torch.autograd.graph.increment_version(param)
+    if _PREP_CACHE_ON:
+        refresh_prepped_kernels(param)
+
+
 class _MaxPoolCL(torch.autograd.Function):
     """qk_maxpool2d_fwd / _bwd on a channels_last buffer (N, H, W, C); windows == strides."""
 
@@ -1146,13 +1214,13 @@ class _CtcFn(torch.autograd.Function):
                                            _ptr(dpred), _ptr(ws), n, _stream(y_pred))
         L.check(rc, 'qk_ctc_batch_cost')
         ctx.save_for_backward(dpred)
-        ctx.loss_scale = float(loss_scale)
+        ctx.loss_scale = loss_scale if isinstance(loss_scale, torch.Tensor) else float(loss_scale)
         return cost.reshape(b, 1)
 
     @staticmethod
     def backward(ctx, dcost):
         dpred, = ctx.saved_tensors
-        if ctx.loss_scale != 1.0:
+        if isinstance(ctx.loss_scale, torch.Tensor) or ctx.loss_scale != 1.0:
             # the product is formed in fp32 and rounded once: d cost / d y can be ~1 / y, dcost ~1 / batch
             return (dpred.float() * (dcost.reshape(-1, 1, 1).float() * ctx.loss_scale)).to(dpred.dtype), None, None, None, None
         return dpred * dcost.reshape(-1, 1, 1).to(dpred.dtype), None, None, None, None
@@ -1191,6 +1259,19 @@ def ctc_supported(y_pred, labels):
             and ctc_shape_supported(y_pred.shape[1], y_pred.shape[2], labels.shape[1]))
 
 
+def loss_scale_arg(loss_scale, device=None):
+    """A loss_scale argument checked without a host read: a positive finite number comes back as a float, a one-element float32
+    device tensor (on `device` when given) as it is."""
+    if isinstance(loss_scale, torch.Tensor):
+        if (loss_scale.dtype != torch.float32 or loss_scale.numel() != 1 or not loss_scale.is_cuda
+                or (device is not None and loss_scale.device != device)):
+            raise TypeError('a tensor loss_scale must be a one-element float32 tensor on the device of the data')
+        return loss_scale.detach()
+    if not (loss_scale > 0 and math.isfinite(loss_scale)):
+        raise ValueError('loss_scale must be a positive finite number')
+    return float(loss_scale)
+
+
 def ctc_batch_cost(y_pred, labels, input_length, label_length, loss_scale=1.0):
     """K.ctc_batch_cost(labels, y_pred, input_length, label_length) (interspeech_model.py:37-39): per-sample CTC cost (B, 1) of
     the softmax outputs y_pred (B, T, C), blank = C - 1, Keras / TensorFlow semantics (include/qk.h: qk_ctc_batch_cost).
@@ -1198,11 +1279,11 @@ def ctc_batch_cost(y_pred, labels, input_length, label_length, loss_scale=1.0):
     loss_scale: the GRADIENT this node sends back is multiplied by it (the cost it returns is not) -- static loss scaling for
     float16 activations: under the CTC cost the gradients of the TIMIT body layers sit at 2^-18.5 (profiles/r04_loss_ab.txt), below
     float16's normal range (2^-14); a power of two (2^12 recommended) moves them into it exactly, and the optimiser undoes it in
-    fp32: `adam_step(grad_scale=1 / (world * loss_scale))`.  bfloat16 / float32 need none."""
+    fp32: `adam_step(grad_scale=1 / (world * loss_scale))`.  bfloat16 / float32 need none.
+    A one-element float32 DEVICE tensor is taken as well (training.GradGuard.loss_scale, the dynamic scale): it is multiplied in on
+    the device when the backward runs and never read on the host."""
     _require_device(y_pred, 'ctc_batch_cost')
-    if not (loss_scale > 0 and math.isfinite(loss_scale)):
-        raise ValueError('loss_scale must be a positive finite number')
-    return _CtcFn.apply(y_pred.contiguous(), labels, input_length, label_length, float(loss_scale))
+    return _CtcFn.apply(y_pred.contiguous(), labels, input_length, label_length, loss_scale_arg(loss_scale, y_pred.device))
 
 
 # ---- CTC decoding (include/qk.h, "CTC decoding") ----------------------------------------------------------------------------------

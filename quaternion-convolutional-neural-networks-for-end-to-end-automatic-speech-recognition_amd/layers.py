@@ -9,7 +9,6 @@ torch ops with the Keras/TensorFlow semantics the models rely on (SURVEY.md 8f r
     (the stock channels_last default the TIMIT model inherits, interspeech_model.py:103 -- for its
     (B, 4F, 41, T) tensor this pools the 41-bin frequency axis 41 -> 14).
 """
-import math
 
 import numpy as np
 import torch
@@ -152,7 +151,10 @@ class _DenseSoftmaxCtcMeanFn(torch.autograd.Function):
         y = Fq.dense_softmax_fwd(x, w.detach(), b.detach() if b is not None else None)
         cost, dpred = Fq.ctc_cost_and_grad(y.view(batch, -1, y.shape[1]), labels, input_length, label_length)
         ctx.save_for_backward(x, w, y, dpred)
-        ctx.params, ctx.scale = (w, b), float(loss_scale) / batch
+        if isinstance(loss_scale, torch.Tensor):       # the device factor goes in beside the upstream scalar (backward)
+            ctx.params, ctx.scale, ctx.scale_dev = (w, b), 1.0 / batch, loss_scale
+        else:
+            ctx.params, ctx.scale, ctx.scale_dev = (w, b), float(loss_scale) / batch, None
         return cost.mean()
 
     @staticmethod
@@ -167,6 +169,8 @@ class _DenseSoftmaxCtcMeanFn(torch.autograd.Function):
             dw = torch.zeros(w.shape, dtype=torch.float32, device=y.device) if want_w else None
             db = torch.zeros(b.shape, dtype=torch.float32, device=y.device) if want_b else None
         g = g.detach().reshape(1).float()
+        if ctx.scale_dev is not None:
+            g = g * ctx.scale_dev.reshape(1)
         dx = Fq.dense_softmax_bwd(x, wk.detach(), y, dpred.view(y.shape), dw, db, dy_scale_dev=g, dy_scale=ctx.scale)
         if direct is not None:
             Fq._grad_ready(w, b)
@@ -177,9 +181,9 @@ class _DenseSoftmaxCtcMeanFn(torch.autograd.Function):
 def dense_softmax_ctc_mean(features, dense, labels, input_length, label_length, loss_scale=1.0):
     """mean_b K.ctc_batch_cost(labels, TimeDistributed(dense)(features), input_length, label_length) for `features` (B, T, in_dim) and
     a built softmax `Dense` layer, through _DenseSoftmaxCtcMeanFn when the hand-written kernels take the shapes; None otherwise (the
-    caller composes it from dense(features), ctc_batch_cost and .mean()).  loss_scale multiplies the gradient only."""
-    if not (loss_scale > 0 and math.isfinite(loss_scale)):
-        raise ValueError('loss_scale must be a positive finite number')
+    caller composes it from dense(features), ctc_batch_cost and .mean()).  loss_scale (a number, or a one-element float32 device
+    tensor that is never read on the host) multiplies the gradient only."""
+    loss_scale = Fq.loss_scale_arg(loss_scale, features.device if features.is_cuda else None)
     if (not features.is_cuda or features.dim() != 3 or not dense.built or dense.kernel.dtype != torch.float32
             or activations.serialize(dense.activation) != 'softmax' or L.dbg(L.QK_DBG_NO_FUSED_SOFTMAX | L.QK_DBG_NO_FUSED_CTC)):
         return None
@@ -190,7 +194,7 @@ def dense_softmax_ctc_mean(features, dense, labels, input_length, label_length, 
         return None
     if not (labels.dim() == 2 and Fq.ctc_shape_supported(t, dense.units, labels.shape[1])):      # (the posteriors this node produces)
         return None
-    return _DenseSoftmaxCtcMeanFn.apply(x2, dense.kernel, dense.bias, labels, input_length, label_length, b, float(loss_scale))
+    return _DenseSoftmaxCtcMeanFn.apply(x2, dense.kernel, dense.bias, labels, input_length, label_length, b, loss_scale)
 
 
 class Dense(Layer):
@@ -390,11 +394,12 @@ class TimeDistributed(Layer):
 
 
 class _GradScale(torch.autograd.Function):
-    """identity forward, gradient x s backward (static loss scaling on the torch path of ctc_batch_cost)"""
+    """identity forward, gradient x s backward (loss scaling on the torch path of ctc_batch_cost); s: a float, or a one-element
+    float32 device tensor read when the backward runs"""
 
     @staticmethod
     def forward(ctx, x, s):
-        ctx.s = s
+        ctx.s = s.detach().reshape(()) if isinstance(s, torch.Tensor) else float(s)
         return x.view_as(x)
 
     @staticmethod
@@ -407,13 +412,16 @@ def ctc_batch_cost(y_pred, labels, input_length, label_length, blank=None, loss_
     the per-sample negative log-likelihood (B, 1).  Keras 2.x hands log(y_pred + epsilon()) to tf.nn.ctc_loss as
     LOGITS, and that op normalises them again (softmax), so the log-probabilities are
     log_softmax(log(y_pred + 1e-7)); ctc_merge_repeated=True, no collapse of repeated labels (TF defaults).
-    loss_scale: multiplies the gradient sent back (not the cost): float16 training, see functional.ctc_batch_cost."""
+    loss_scale: multiplies the gradient sent back (not the cost): float16 training, see functional.ctc_batch_cost (a number or a
+    one-element float32 device tensor)."""
     if (blank is None and y_pred.is_cuda and Fq.ctc_supported(y_pred, labels) and not L.dbg(L.QK_DBG_NO_FUSED_CTC)):
         return Fq.ctc_batch_cost(y_pred, labels, input_length, label_length, loss_scale=loss_scale)        # one HIP launch: cost + gradient
     blank = y_pred.shape[-1] - 1 if blank is None else blank
     yp = y_pred.float()
-    if loss_scale != 1.0:
-        yp = _GradScale.apply(yp, float(loss_scale))          # (in fp32, in front of the cast back to y_pred's dtype)
+    if isinstance(loss_scale, torch.Tensor):
+        loss_scale = Fq.loss_scale_arg(loss_scale, y_pred.device)
+    if isinstance(loss_scale, torch.Tensor) or loss_scale != 1.0:
+        yp = _GradScale.apply(yp, loss_scale)          # (in fp32, in front of the cast back to y_pred's dtype)
     logp = torch.log_softmax(torch.log(yp + 1e-7), dim=-1).transpose(0, 1)
     loss = F.ctc_loss(logp, labels.long(), input_length.reshape(-1).long(), label_length.reshape(-1).long(),
                       blank=blank, reduction='none', zero_infinity=False)

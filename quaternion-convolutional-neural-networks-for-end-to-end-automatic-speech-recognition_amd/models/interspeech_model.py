@@ -322,11 +322,14 @@ class TimitQCNN(torch.nn.Module):
         """What training the reference model minimises: mean CTC cost over the batch (the usual
         `loss={'ctc': lambda y_true, y_pred: y_pred}` compile) + the regularisation terms.  loss_scale changes GRADIENTS only:
         the regulariser goes through the same identity-forward / scaled-backward node as the CTC cost, so that ONE grad_scale in
-        the optimiser undoes both and the value returned (what gets logged) is the unscaled loss."""
+        the optimiser undoes both and the value returned (what gets logged) is the unscaled loss.  loss_scale is a number or a
+        one-element float32 device tensor (training.GradGuard.loss_scale), here and in ctc_loss / ctc_mean_loss."""
         reg = self.regularization_loss()
-        if loss_scale != 1.0:
+        if isinstance(loss_scale, torch.Tensor):
+            loss_scale = Fq.loss_scale_arg(loss_scale, x.device)
+        if isinstance(loss_scale, torch.Tensor) or loss_scale != 1.0:
             from ..layers import _GradScale
-            reg = _GradScale.apply(reg, float(loss_scale))
+            reg = _GradScale.apply(reg, loss_scale)
         return self.ctc_mean_loss(x, labels, input_length, label_length, loss_scale=loss_scale) + reg
 
 
