@@ -19,6 +19,10 @@ prints its held-out perplexity, and adds to every evaluation the PER(39) of the 
 fused in (--lm-weight, --insertion-bonus).
 
     python examples/train_timit.py --timit /path/to/TIMIT --eval-every 200 --lm-order 2 --lm-weight 0.5 --beam-width 16
+
+--specaug augments the TRAINING batches with qcnn_amd.features.SpecAugment (time warp, frequency and time masks on the device, one
+launch, seeded from --seed; --time-warp, --freq-masks, --freq-width, --time-masks, --time-width, --time-ratio).  Evaluation batches
+are never augmented.  The default policy is scaled from the paper's LibriSpeech policy; no phone error rate has been measured with it.
 """
 import argparse
 import os
@@ -32,7 +36,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
 import qcnn_amd  # noqa: E402,F401
 from qcnn_amd import dp, functional as F  # noqa: E402
 from qcnn_amd.data import TIMIT_PHONES_61, read_audio, read_phn, timit_61_to_39_class_map  # noqa: E402
-from qcnn_amd.features import quaternion_fbank  # noqa: E402
+from qcnn_amd.features import SpecAugment, quaternion_fbank  # noqa: E402
 from qcnn_amd.lm import NgramLM  # noqa: E402
 from qcnn_amd.models import getTimitModel2D  # noqa: E402
 from qcnn_amd.training import GradGuard  # noqa: E402
@@ -67,8 +71,9 @@ def length_batches(utts, batch):
     return [order[i:i + batch] for i in range(0, len(order), batch)]
 
 
-def to_device(utts, idx, dev, dtype):
-    """Features (quaternion_fbank, per-utterance normalisation), frame counts, padded labels and label lengths of one batch."""
+def to_device(utts, idx, dev, dtype, augment=None):
+    """Features (quaternion_fbank, per-utterance normalisation; SpecAugment when `augment` is given: training batches only), frame
+    counts, padded labels and label lengths of one batch."""
     n = [len(utts[i][0]) for i in idx]
     wave = np.zeros((len(idx), max(n)), dtype=np.int16)
     lab_len = [len(utts[i][1]) for i in idx]
@@ -77,7 +82,7 @@ def to_device(utts, idx, dev, dtype):
         wave[r, :n[r]] = utts[i][0]
         labels[r, :lab_len[r]] = utts[i][1]
     x, frame_lengths = quaternion_fbank(torch.from_numpy(wave).to(dev), torch.tensor(n, dtype=torch.int32), normalize='utterance',
-                                        dtype=dtype)
+                                        dtype=dtype, augment=augment)
     labels = torch.from_numpy(labels).to(dev)
     label_length = torch.tensor(lab_len, dtype=torch.int32, device=dev)[:, None]
     return x, frame_lengths[:, None], labels, label_length
@@ -105,6 +110,13 @@ def main():
     ap.add_argument('--dtype', default='bfloat16', choices=['bfloat16', 'float16'], help='activation dtype')
     ap.add_argument('--dynamic-loss-scale', action='store_true',
                     help='loss scale on the device, starting at 2^12: halved on an overflowing (skipped) step, doubled after 2000 good ones')
+    ap.add_argument('--specaug', action='store_true', help='SpecAugment on the training batches (never on evaluation batches)')
+    ap.add_argument('--time-warp', type=int, default=5, help='SpecAugment: a frame moves by up to this many frames (0: no warp)')
+    ap.add_argument('--freq-masks', type=int, default=2)
+    ap.add_argument('--freq-width', type=int, default=8, help='largest frequency mask, rows of 41')
+    ap.add_argument('--time-masks', type=int, default=2)
+    ap.add_argument('--time-width', type=int, default=25, help='largest time mask, frames ...')
+    ap.add_argument('--time-ratio', type=float, default=0.2, help='... and at most this share of the utterance')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
@@ -137,6 +149,10 @@ def main():
     flat = dp.FlatParams([p for p in model.parameters() if p.requires_grad])   # the l2 terms come through training_loss
     m, v = torch.zeros_like(flat.param), torch.zeros_like(flat.param)
     rng = np.random.RandomState(args.seed)
+    augment = None
+    if args.specaug:
+        augment = SpecAugment(time_warp=args.time_warp, freq_masks=args.freq_masks, freq_width=args.freq_width, time_masks=args.time_masks,
+                              time_width=args.time_width, time_ratio=args.time_ratio, seed=args.seed & 0xFFFFFFFF)
     # clipping / float16 / dynamic scaling: the guarded step (qcnn_amd.training.GradGuard).  Norm, overflow check, clip and scale
     # update all happen on the device, and so does the step count (a skipped step does not advance it).
     guard = None
@@ -145,7 +161,7 @@ def main():
                           loss_scale=2.0 ** 12 if dtype == torch.float16 or args.dynamic_loss_scale else 1.0)
         step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
     for step in range(1, args.steps + 1):
-        x, il, labels, ll = to_device(train, batches[rng.randint(len(batches))], dev, dtype)
+        x, il, labels, ll = to_device(train, batches[rng.randint(len(batches))], dev, dtype, augment)
         if guard is None:
             loss = model.training_loss(x, labels, il, ll)
             loss.backward()

@@ -501,6 +501,59 @@ int qk_fbank_quaternion(int32_t wave_dtype, int32_t batch, int64_t max_samples, 
                         const int32_t *mel_bins, int32_t append_energy, int32_t delta_n, int32_t normalize, int32_t out_dtype, void *out,
                         int32_t *frame_lengths, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- SpecAugment ------------------------------------------------------------------------------------------------------------
+ * Time warp, frequency masks and time masks (Park et al., 2019) on the model's channels_first input, as ONE launch:
+ * x and out are contiguous (batch, planes, rows, frames), in_dtype / out_dtype (qk_dtype_t) any of fp32, bf16, fp16 on either side.
+ * One time-frequency cell of the input is one quaternion (planes r / i / j / k = the static value and its first three time
+ * derivatives), so every plane of an utterance gets the SAME warp and the SAME masks.  out must not overlap x (the warp reads
+ * neighbouring frames): QK_ERR_INVALID_ARG.  The call does not synchronise, needs no workspace and uses no atomics; the draws are a
+ * counter-based hash of (seed, *counter_dev, utterance, draw index) as for qk_postop_t.drop_seed_dev: bit-repeatable, and new on
+ * every replay of a captured graph whose counter a device op advances.  seed and utterance index enter the key as a sum: callers
+ * that augment different data with one policy (data-parallel ranks) use seeds at least `batch` apart.
+ *
+ * Random draws (uint32 arithmetic, mod 2^32):
+ *   fmix(h):  h ^= h>>16; h *= 0x85EBCA6B; h ^= h>>13; h *= 0xC2B2AE35; h ^= h>>16
+ *   key = seed + 0x9E3779B1 * counter,  counter = counter_dev ? *counter_dev : 0
+ *   u(b,k) = fmix(fmix(key + b) ^ (k * 0x9E3779B1 + 0x7F4A7C15))
+ *   randint(b,k,m) = (uint64(u(b,k)) * m) >> 32, a value in [0, m), for m >= 1
+ *   draw indices k: 0 the warp centre, 1 the warp shift; 2+2i and 3+2i the width and start of frequency mask i; 18+2i and 19+2i
+ *   the width and start of time mask i.
+ * Utterance length: per utterance b, n = clamp(lengths[b], 0, frames).
+ * Time warp: active iff time_warp = W >= 1 and n >= 2W + 3.
+ *   c = W + 1 + randint(b,0, n - 2W - 2);  w = randint(b,1, 2W + 1) - W;  c' = c + w, which lies in [1, n-2].
+ *   t <= c':  num = t c, den = c'.       t > c':  num = c (n-1-c') + (t-c') (n-1-c), den = n-1-c'.
+ *   Index arithmetic is exact integer arithmetic, 64-bit where 32 bits could overflow.
+ *   i0 = num / den, r = num % den, frac = float(r) / float(den);  y = x[i0] + frac (x[min(i0+1, n-1)] - x[i0]), computed in fp32.
+ *   Frames 0, c' and n-1 map onto frames 0, c and n-1 exactly.  When the warp is inactive, c = w = 0 and y = x.
+ * Frequency mask i < freq_masks:  fw = randint(b,2+2i, min(freq_width, rows) + 1);  f0 = randint(b,3+2i, rows - fw + 1).
+ * Time mask i < time_masks:  cap = min(time_width, (int)floorf((float)n * time_ratio)), one fp32 product;
+ *   tw = randint(b,18+2i, cap + 1);  t0 = randint(b,19+2i, n - tw + 1).
+ * Output: for t < n the value is `fill` if the row lies in any frequency mask [f0, f0 + fw) or the frame lies in any time mask
+ *   [t0, t0 + tw), otherwise the warped value; the same cells are masked in every plane; masks apply after the warp; the value
+ *   is rounded once to out_dtype at the store.  For t >= n: out = x converted to out_dtype; nothing from a frame >= n reaches a
+ *   frame < n.  With no warp, no masks and equal dtypes the result is a bit copy.
+ * Plan row (plan: (batch, QK_SPECAUG_PLAN_WORDS) int32, or NULL): {n, c, w, 0, (f0, fw) x 8, (t0, tw) x 8}, unused masks 0, 0.
+ * QK_ERR_INVALID_ARG: mask counts outside 0 .. QK_SPECAUG_MAX_MASKS, negative widths or a negative warp, time_ratio outside [0, 1]
+ *   or not finite, fill not finite, batch / planes / rows / frames < 1, a NULL x / lengths / policy / out.  QK_ERR_UNSUPPORTED: a
+ *   tensor of 2^31 elements or more.
+ * Deviation from the paper: the derivative planes are warped like the static plane; they are NOT rescaled by the local slope of
+ * the warp (augmenting the static rows before the deltas, inside the front end's kernels, would be exact). */
+#define QK_SPECAUG_MAX_MASKS 8
+#define QK_SPECAUG_PLAN_WORDS 36
+typedef struct qk_specaug_t {
+    int32_t time_warp;       /* W: the warp moves one frame by up to W frames; 0: off */
+    int32_t freq_masks;      /* 0 .. QK_SPECAUG_MAX_MASKS */
+    int32_t freq_width;      /* largest width of a frequency mask, rows */
+    int32_t time_masks;      /* 0 .. QK_SPECAUG_MAX_MASKS */
+    int32_t time_width;      /* largest width of a time mask, frames ... */
+    float time_ratio;        /* ... and at most this share of the utterance's n frames; in [0, 1] */
+    float fill;              /* value of a masked cell (0 = the row mean after per-utterance normalisation) */
+    uint32_t seed;
+} qk_specaug_t;
+int qk_spec_augment(int32_t in_dtype, int32_t out_dtype, int32_t batch, int32_t planes, int32_t rows, int32_t frames,
+                    const void *x, const int32_t *lengths, const qk_specaug_t *policy, const uint32_t *counter_dev /* NULL: 0 */,
+                    void *out, int32_t *plan /* (batch, 36) or NULL */, void *stream);
+
 /* Softmax over the last axis of a (rows, cols <= 64) matrix, one wave per row -- the activation of the model's
  * TimeDistributed(Dense(62, activation='softmax')) output layer (models/interspeech_model.py:171-175) and its autodiff:
  *   fwd   y = softmax(logits + bias)          logits: fp32 (the GEMM's fp32 output), bias: fp32 or NULL, y: `dtype`

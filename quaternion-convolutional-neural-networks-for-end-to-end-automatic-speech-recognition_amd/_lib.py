@@ -30,6 +30,7 @@ QK_WAVE_F32, QK_WAVE_I16 = 0, 1                                  # acoustic fron
 QK_WINDOW_RECT, QK_WINDOW_HAMMING = 0, 1
 QK_FBANK_NORM_NONE, QK_FBANK_NORM_UTTERANCE = 0, 1
 QK_FBANK_MAX_FILT = 128
+QK_SPECAUG_MAX_MASKS, QK_SPECAUG_PLAN_WORDS = 8, 36             # SpecAugment (qk_spec_augment)
 QK_ERR_INVALID_ARG, QK_ERR_UNSUPPORTED, QK_ERR_WORKSPACE, QK_ERR_LAUNCH = -1, -2, -3, -4
 QK_PATH_NAMES = {0: 'none', 1: 'mfma16', 2: 'mfma16_band', 3: 'fp32_mfma', 4: 'mfma16_point', 5: 'mfma16_small'}               # qk_last_path
 
@@ -80,6 +81,12 @@ class GradGuardConfig(ctypes.Structure):
     _fields_ = [('clipnorm', ctypes.c_float), ('clipvalue', ctypes.c_float), ('dynamic', I32),
                 ('growth_factor', ctypes.c_float), ('backoff_factor', ctypes.c_float), ('growth_interval', I32),
                 ('min_scale', ctypes.c_float), ('max_scale', ctypes.c_float)]
+
+
+class SpecAugPolicy(ctypes.Structure):
+    """qk_specaug_t (include/qk.h)"""
+    _fields_ = [('time_warp', I32), ('freq_masks', I32), ('freq_width', I32), ('time_masks', I32), ('time_width', I32),
+                ('time_ratio', ctypes.c_float), ('fill', ctypes.c_float), ('seed', ctypes.c_uint32)]
 
 
 # qk_grad_guard_state_t: eight 4-byte fields in device memory; (name, is_float) in order
@@ -141,6 +148,7 @@ SYMBOLS = {
     'qk_fbank_workspace_bytes': (_SZ, [I32, I32, I32, I32]),
     'qk_fbank_quaternion': (ctypes.c_int, [I32, I32, ctypes.c_int64, _VP, _VP, I32, I32, I32, I32, ctypes.c_float, I32, I32,
                                            ctypes.POINTER(I32), I32, I32, I32, I32, _VP, _VP, _VP, _SZ, _VP]),
+    'qk_spec_augment': (ctypes.c_int, [I32, I32, I32, I32, I32, I32, _VP, _VP, ctypes.POINTER(SpecAugPolicy), _VP, _VP, _VP, _VP]),
     'qk_softmax_rows_fwd': (ctypes.c_int, [I32, ctypes.c_int64, I32, _VP, _VP, _VP, _VP]),
     'qk_softmax_rows_bwd': (ctypes.c_int, [I32, ctypes.c_int64, I32, _VP, _VP, _VP, _VP, _VP]),
     'qk_dense_softmax_supported': (ctypes.c_int, [I32, ctypes.c_int64, I32, I32]),

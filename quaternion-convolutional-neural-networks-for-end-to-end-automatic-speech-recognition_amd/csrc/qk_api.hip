@@ -1222,6 +1222,40 @@ int qk_fbank_quaternion(int32_t wave_dtype, int32_t batch, int64_t max_samples, 
                                      (hipStream_t)stream), "qk_fbank_quaternion");
 }
 
+int qk_spec_augment(int32_t in_dtype, int32_t out_dtype, int32_t batch, int32_t planes, int32_t rows, int32_t frames,
+                    const void *x, const int32_t *lengths, const qk_specaug_t *policy, const uint32_t *counter_dev,
+                    void *out, int32_t *plan, void *stream)
+{
+    if (batch < 1 || planes < 1 || rows < 1 || frames < 1 || in_dtype < QK_F32 || in_dtype > QK_F16 || out_dtype < QK_F32 || out_dtype > QK_F16) {
+        set_error("spec_augment: bad arguments (batch %d, planes %d, rows %d, frames %d, dtypes %d / %d)", batch, planes, rows, frames, in_dtype, out_dtype);
+        return QK_ERR_INVALID_ARG;
+    }
+    if (!x || !lengths || !policy || !out) { set_error("spec_augment: NULL argument"); return QK_ERR_INVALID_ARG; }
+    const qk_specaug_t &p = *policy;
+    if (p.freq_masks < 0 || p.freq_masks > QK_SPECAUG_MAX_MASKS || p.time_masks < 0 || p.time_masks > QK_SPECAUG_MAX_MASKS) {
+        set_error("spec_augment: freq_masks %d / time_masks %d outside 0 .. %d", p.freq_masks, p.time_masks, QK_SPECAUG_MAX_MASKS);
+        return QK_ERR_INVALID_ARG;
+    }
+    if (p.time_warp < 0 || p.freq_width < 0 || p.time_width < 0) {
+        set_error("spec_augment: time_warp %d, freq_width %d and time_width %d must be >= 0", p.time_warp, p.freq_width, p.time_width);
+        return QK_ERR_INVALID_ARG;
+    }
+    if (!isfinite(p.time_ratio) || p.time_ratio < 0.f || p.time_ratio > 1.f || !isfinite(p.fill)) {
+        set_error("spec_augment: time_ratio %g must lie in [0, 1] and fill %g be finite", (double)p.time_ratio, (double)p.fill);
+        return QK_ERR_INVALID_ARG;
+    }
+    const long long count = (long long)batch * planes * rows * frames;
+    if (count > INT_MAX) { set_error("spec_augment: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
+    const size_t in_bytes = (size_t)count * elem_bytes(in_dtype), out_bytes = (size_t)count * elem_bytes(out_dtype);
+    if (!aligned(x, elem_bytes(in_dtype)) || !aligned(out, elem_bytes(out_dtype)) || (plan && !aligned(plan, 4))) {
+        set_error("spec_augment: x, out and plan must be aligned to their element size"); return QK_ERR_INVALID_ARG;
+    }
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(x), oa = reinterpret_cast<uintptr_t>(out);
+    if (xa < oa + out_bytes && oa < xa + in_bytes) { set_error("spec_augment: out overlaps x (the warp reads neighbouring frames)"); return QK_ERR_INVALID_ARG; }
+    return check_launch(launch_spec_augment(in_dtype, out_dtype, batch, planes, rows, frames, x, lengths, p, counter_dev, out, plan,
+                                            (hipStream_t)stream), "qk_spec_augment");
+}
+
 int qk_softmax_rows_fwd(int32_t dtype, int64_t rows, int32_t cols, const float *logits, const float *bias, void *y, void *stream)
 {
     if (!logits || !y || rows < 0 || cols < 1 || cols > 64 || dtype < QK_F32 || dtype > QK_F16) { set_error("qk_softmax_rows_fwd: bad argument (1 <= cols <= 64)"); return QK_ERR_INVALID_ARG; }

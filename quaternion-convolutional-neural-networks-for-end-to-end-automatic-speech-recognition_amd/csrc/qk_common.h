@@ -367,6 +367,9 @@ int fbank_tile(int L, int S);
 size_t fbank_workspace_bytes(int B, int T, int F, bool norm);
 int launch_fbank(int wave_dtype, const void *wave, const int *lengths, const FbankGeom &g, int N, bool norm, int out_dtype, void *out,
                  int *frame_lengths, void *ws, hipStream_t stream);
+// SpecAugment (qk_specaug.hip)
+int launch_spec_augment(int in_dtype, int out_dtype, int B, int P, int R, int T, const void *x, const int *lengths,
+                        const qk_specaug_t &pol, const unsigned *counter, void *out, int *plan, hipStream_t stream);
 int launch_relayout16(const void *src, void *dst, int n, int A, int B, hipStream_t stream);     // (n, A, B) -> (n, B, A), 16-bit
 struct PoolGeom { int batch, ih, iw, C, wh, ww, oh, ow; };
 int launch_maxpool(int dtype, bool backward, const void *x, const void *dy, void *out, const PoolGeom &g, hipStream_t stream);

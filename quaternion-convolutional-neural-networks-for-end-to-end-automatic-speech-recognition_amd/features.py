@@ -58,7 +58,7 @@ def mel_filterbank(nfilt=40, nfft=512, sample_rate=16000, lowfreq=0, highfreq=No
 
 
 def quaternion_fbank(wave, lengths=None, sample_rate=16000, winlen=0.025, winstep=0.01, nfilt=40, nfft=512, lowfreq=0, highfreq=None,
-                     preemph=0.97, window='rect', delta_n=2, append_energy=True, normalize=None, dtype=torch.float32):
+                     preemph=0.97, window='rect', delta_n=2, append_energy=True, normalize=None, dtype=torch.float32, augment=None):
     """Quaternion filter-bank features of a batch of waveforms, on the device.
 
     wave: (B, n_max) or (n_max,) int16 / float32 CUDA tensor; lengths: samples per utterance (B,) (default n_max each; clamped to
@@ -69,7 +69,13 @@ def quaternion_fbank(wave, lengths=None, sample_rate=16000, winlen=0.025, winste
 
     Returns (x, frame_lengths): x (B, 4, nfilt [+ 1], T) in `dtype` with T = num_frames(n_max) and frames t >= frame_lengths[b]
     zero; frame_lengths (B,) int32, ready to serve as the CTC input_length.  Limits: nfft a power of two in [256, 1024] and at least
-    the frame length, nfilt <= 128, 1 <= delta_n <= 4."""
+    the frame length, nfilt <= 128, 1 <= delta_n <= 4.
+
+    augment: a SpecAugment policy (training batches only).  The features are then computed in float32, after any normalisation,
+    augmented with the frame lengths as the utterance lengths, and rounded once to `dtype`; after normalize='utterance' a fill of 0
+    is the per-row mean.  None (the default): no augmentation, the calls are exactly those of the plain front end."""
+    if augment is not None and not isinstance(augment, SpecAugment):
+        raise TypeError('quaternion_fbank: augment must be a SpecAugment or None, got %r' % (augment,))
     if window not in WINDOWS:
         raise ValueError('quaternion_fbank: window must be one of %s, got %r' % (sorted(WINDOWS), window))
     if normalize not in NORMALIZE:
@@ -108,5 +114,79 @@ def quaternion_fbank(wave, lengths=None, sample_rate=16000, winlen=0.025, winste
         lengths = lengths.reshape(-1).to(device=wave.device, dtype=torch.int32)
     bins = _mel_bins(nfilt, nfft, sample_rate, lowfreq, highfreq).astype(np.int64).tolist()
     frames = num_frames(n_max, sample_rate, winlen, winstep)
-    return F.fbank_quaternion(wave, lengths, frames, frame_len, frame_step, nfft, preemph, WINDOWS[window], bins, append_energy, delta_n,
-                              NORMALIZE[normalize], dtype)
+    if augment is None:
+        return F.fbank_quaternion(wave, lengths, frames, frame_len, frame_step, nfft, preemph, WINDOWS[window], bins, append_energy,
+                                  delta_n, NORMALIZE[normalize], dtype)
+    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise TypeError('quaternion_fbank: unsupported output dtype %s (float32, bfloat16, float16)' % dtype)
+    x, flen = F.fbank_quaternion(wave, lengths, frames, frame_len, frame_step, nfft, preemph, WINDOWS[window], bins, append_energy,
+                                 delta_n, NORMALIZE[normalize], torch.float32)
+    return augment(x, flen, dtype=dtype), flen
+
+
+class SpecAugment(object):
+    """A SpecAugment policy (Park et al., 2019) for the quaternion filter-bank input, with its own device counter.
+
+        aug = SpecAugment(seed=args.seed)
+        x, il = quaternion_fbank(wave, lengths, normalize='utterance', dtype=torch.bfloat16, augment=aug)     # training batches only
+
+    Per utterance: one time warp that moves a frame by up to time_warp frames, freq_masks masks of up to freq_width rows and
+    time_masks masks of up to min(time_width, time_ratio * frames) frames, written as `fill` -- one launch (functional.spec_augment;
+    semantics: include/qk.h, "SpecAugment").  A time-frequency cell is one quaternion, so all four planes get the same warp and the
+    same masks; the derivative planes are warped like the static plane and NOT rescaled by the warp's local slope.
+
+    The defaults are the paper's LibriSpeech policy scaled to 41 rows and TIMIT-length utterances (W 80 -> 5, F 27 of 80 -> 8 of
+    41, T 100 -> 25, two masks of each kind, p = 0.2).  Nobody has measured a phone error rate with them: treat them as a starting
+    point, not as tuned values.
+
+    The draws are a hash of (seed, counter, utterance index): bit-repeatable from the seed.  __call__ advances the counter with a
+    device op behind the kernel, so a captured graph draws new masks on every replay and nothing is read on the host.
+    Data-parallel ranks must pass DIFFERENT seeds, or every rank masks its utterance b like every other's; seed and utterance index
+    enter the hash as a sum, so keep the seeds at least a batch apart (e.g. seed + 65536 * rank).
+    state_dict() / load_state_dict() carry the seed and the counter (reading the counter synchronises)."""
+
+    def __init__(self, time_warp=5, freq_masks=2, freq_width=8, time_masks=2, time_width=25, time_ratio=0.2, fill=0.0, seed=0):
+        F._specaug_policy('SpecAugment', time_warp, freq_masks, freq_width, time_masks, time_width, time_ratio, fill, seed)
+        self.policy = dict(time_warp=time_warp, freq_masks=freq_masks, freq_width=freq_width, time_masks=time_masks,
+                           time_width=time_width, time_ratio=float(time_ratio), fill=float(fill), seed=seed)
+        self._counter = None            # one int32 on the device of the first call; the kernel reads its 32 bits as unsigned
+        self._pending = 0               # counter value to start from (load_state_dict before the first call)
+        self.last_plan = None
+
+    @property
+    def seed(self):
+        return self.policy['seed']
+
+    def _counter_on(self, device):
+        if self._counter is None:
+            v = self._pending - (1 << 32) if self._pending >= 1 << 31 else self._pending
+            self._counter = torch.full((1,), v, dtype=torch.int32, device=device)
+        elif self._counter.device != device:
+            raise ValueError('SpecAugment: this policy\'s counter lives on %s, the input on %s' % (self._counter.device, device))
+        return self._counter
+
+    def __call__(self, x, lengths, dtype=None):
+        """Augmented copy of x (B, planes, rows, T) in `dtype` (default x.dtype); the plan of the call is kept in .last_plan."""
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise RuntimeError('SpecAugment: got a CPU tensor. SpecAugment runs only on the MI355X HIP path (libqk_hip.so); there is '
+                               'no CPU fallback.')
+        counter = self._counter_on(x.device)
+        out, self.last_plan = F.spec_augment(x, lengths, counter=counter, dtype=dtype, return_plan=True, **self.policy)
+        counter.add_(1)                 # wraps mod 2^32, like the kernel's key
+        return out
+
+    def state_dict(self):
+        counter = self._pending if self._counter is None else int(self._counter.item()) & 0xFFFFFFFF
+        return {'seed': self.policy['seed'], 'counter': counter}
+
+    def load_state_dict(self, d):
+        """Takes what state_dict() gave; checked on the host before anything is written."""
+        seed, counter = d['seed'], d['counter']
+        for name, v in (('seed', seed), ('counter', counter)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError('SpecAugment.load_state_dict: %s must be an integer in [0, 2^32), got %r' % (name, v))
+        self.policy['seed'] = seed
+        if self._counter is None:
+            self._pending = counter
+        else:
+            self._counter.fill_(counter - (1 << 32) if counter >= 1 << 31 else counter)

@@ -1497,3 +1497,73 @@ def fbank_quaternion(wave, lengths, frames, frame_len, frame_step, nfft, preemph
                                          _ptr(out), _ptr(flen), _ptr(ws), n, _stream(wave))
     L.check(rc, 'qk_fbank_quaternion')
     return out, flen
+
+
+# ---- SpecAugment (include/qk.h, "SpecAugment") ----------------------------------------------------------------------------------
+def _specaug_policy(what, time_warp, freq_masks, freq_width, time_masks, time_width, time_ratio, fill, seed):
+    """The checked qk_specaug_t of a policy; ValueError / TypeError on the host, before any device is touched."""
+    vals = {}
+    for name, v in (('time_warp', time_warp), ('freq_masks', freq_masks), ('freq_width', freq_width), ('time_masks', time_masks),
+                    ('time_width', time_width), ('seed', seed)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError('%s: %s must be an integer, got %r' % (what, name, v))
+        vals[name] = v
+    for name in ('freq_masks', 'time_masks'):
+        if not 0 <= vals[name] <= L.QK_SPECAUG_MAX_MASKS:
+            raise ValueError('%s: %s %d outside 0 .. %d' % (what, name, vals[name], L.QK_SPECAUG_MAX_MASKS))
+    for name in ('time_warp', 'freq_width', 'time_width'):
+        if not 0 <= vals[name] < 2 ** 30:
+            raise ValueError('%s: %s must be >= 0 (and < 2^30), got %d' % (what, name, vals[name]))
+    if not 0 <= vals['seed'] <= 0xFFFFFFFF:
+        raise ValueError('%s: seed must fit 32 unsigned bits, got %d' % (what, vals['seed']))
+    for name, v in (('time_ratio', time_ratio), ('fill', fill)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError('%s: %s must be a finite number, got %r' % (what, name, v))
+    if not 0.0 <= time_ratio <= 1.0:
+        raise ValueError('%s: time_ratio %r outside [0, 1]' % (what, time_ratio))
+    return L.SpecAugPolicy(vals['time_warp'], vals['freq_masks'], vals['freq_width'], vals['time_masks'], vals['time_width'],
+                           float(time_ratio), float(fill), vals['seed'])
+
+
+def spec_augment(x, lengths, *, time_warp=0, freq_masks=0, freq_width=0, time_masks=0, time_width=0, time_ratio=1.0, fill=0.0, seed=0,
+                 counter=None, dtype=None, return_plan=False):
+    """SpecAugment of the model's channels_first input as one launch (qk_spec_augment; semantics: include/qk.h, "SpecAugment").
+
+    x (B, planes, rows, T) float32 / bfloat16 / float16 on the device; lengths (B,) valid frames per utterance (clamped to [0, T]).
+    Per utterance: a time warp that moves one frame by up to time_warp frames (linear interpolation, fp32), freq_masks masks of up
+    to freq_width rows, time_masks masks of up to min(time_width, time_ratio n) frames, written as `fill`.  Every plane of an
+    utterance gets the same warp and masks (a cell is one quaternion); the derivative planes are NOT rescaled by the warp's slope.
+    Frames >= lengths[b] are copied.  The draws are a hash of (seed, counter, utterance): equal arguments give equal bits.
+    counter: one-element int32 / uint32 DEVICE tensor read by the kernel (None: 0) -- advance it with a device op and a captured
+    graph draws new masks on every replay.  dtype: output dtype (default x.dtype).  Returns a new tensor (never x itself), or
+    (out, plan) with return_plan: plan (B, 36) int32 on the device = {n, c, w, 0, (f0, fw) x 8, (t0, tw) x 8}.  No host sync."""
+    what = 'spec_augment'
+    pol = _specaug_policy(what, time_warp, freq_masks, freq_width, time_masks, time_width, time_ratio, fill, seed)
+    if dtype is None and torch.is_tensor(x):
+        dtype = x.dtype
+    if dtype not in _DTYPES:
+        raise TypeError('%s: unsupported output dtype %s (float32, bfloat16, float16)' % (what, dtype))
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError('%s: got a CPU tensor. SpecAugment runs only on the MI355X HIP path (libqk_hip.so); there is no CPU '
+                           'fallback.' % what)
+    if x.dtype not in _DTYPES:
+        raise TypeError('%s: unsupported input dtype %s (float32, bfloat16, float16)' % (what, x.dtype))
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError('%s: x must be a non-empty (B, planes, rows, T) tensor, got shape %s' % (what, tuple(x.shape)))
+    b, planes, rows, frames = x.shape
+    lengths = lengths if torch.is_tensor(lengths) else torch.as_tensor(lengths)
+    if lengths.numel() != b:
+        raise ValueError('%s: lengths must have B = %d entries, got %d' % (what, b, lengths.numel()))
+    lengths = lengths.reshape(-1).to(device=x.device, dtype=torch.int32).contiguous()
+    if counter is not None:
+        if (not torch.is_tensor(counter) or counter.device != x.device or counter.numel() != 1
+                or counter.dtype not in (torch.int32, torch.uint32)):
+            raise ValueError('%s: counter must be a one-element int32 / uint32 tensor on %s' % (what, x.device))
+    x = x.contiguous()
+    out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    plan = torch.empty((b, L.QK_SPECAUG_PLAN_WORDS), dtype=torch.int32, device=x.device) if return_plan else None
+    with _on_device(x.device):
+        rc = L.lib().qk_spec_augment(_DTYPES[x.dtype], _DTYPES[dtype], b, planes, rows, frames, _ptr(x), _ptr(lengths), ctypes.byref(pol),
+                                     _ptr(counter), _ptr(out), _ptr(plan), _stream(x))
+    L.check(rc, 'qk_spec_augment')
+    return (out, plan) if return_plan else out
