@@ -23,8 +23,15 @@ fused in (--lm-weight, --insertion-bonus).
 --specaug augments the TRAINING batches with qcnn_amd.features.SpecAugment (time warp, frequency and time masks on the device, one
 launch, seeded from --seed; --time-warp, --freq-masks, --freq-width, --time-masks, --time-width, --time-ratio).  Evaluation batches
 are never augmented.  The default policy is scaled from the paper's LibriSpeech policy; no phone error rate has been measured with it.
+
+--speed-perturb resamples every utterance of a TRAINING batch by one of --speeds (default 0.9,1.0,1.1; tempo and pitch change
+together, as `sox speed` does) and multiplies it by a gain drawn from --volume LO,HI (default 1,1), on the device in front of the
+filter bank (qcnn_amd.features.SpeedPerturb, one launch, seeded from --seed).  The labels are unchanged: a sped-up utterance has
+fewer frames for the same labels.  Evaluation batches are never perturbed; it combines with --specaug.  No phone error rate has been
+measured with it.
 """
 import argparse
+import fractions
 import os
 import sys
 import types
@@ -36,7 +43,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
 import qcnn_amd  # noqa: E402,F401
 from qcnn_amd import dp, functional as F  # noqa: E402
 from qcnn_amd.data import TIMIT_PHONES_61, read_audio, read_phn, timit_61_to_39_class_map  # noqa: E402
-from qcnn_amd.features import SpecAugment, quaternion_fbank  # noqa: E402
+from qcnn_amd.features import SpecAugment, SpeedPerturb, quaternion_fbank  # noqa: E402
 from qcnn_amd.lm import NgramLM  # noqa: E402
 from qcnn_amd.models import getTimitModel2D  # noqa: E402
 from qcnn_amd.training import GradGuard  # noqa: E402
@@ -71,9 +78,25 @@ def length_batches(utts, batch):
     return [order[i:i + batch] for i in range(0, len(order), batch)]
 
 
-def to_device(utts, idx, dev, dtype, augment=None):
-    """Features (quaternion_fbank, per-utterance normalisation; SpecAugment when `augment` is given: training batches only), frame
-    counts, padded labels and label lengths of one batch."""
+def parse_speeds(text):
+    """'0.9,1.0,1.1' -> ((9, 10), (1, 1), (11, 10)): each speed as the closest fraction with a denominator <= 32."""
+    out = []
+    for word in text.split(','):
+        f = fractions.Fraction(word.strip()).limit_denominator(32)
+        if not 0 < f.numerator <= 32:
+            raise argparse.ArgumentTypeError('speed %r: not a fraction of two numbers in 1 .. 32' % word)
+        out.append((f.numerator, f.denominator))
+    return tuple(out)
+
+
+def parse_volume(text):
+    lo, hi = (float(v) for v in text.split(','))
+    return lo, hi
+
+
+def to_device(utts, idx, dev, dtype, augment=None, wave_augment=None):
+    """Features (quaternion_fbank, per-utterance normalisation; SpeedPerturb on the waveforms when `wave_augment` is given and
+    SpecAugment when `augment` is: training batches only), frame counts, padded labels and label lengths of one batch."""
     n = [len(utts[i][0]) for i in idx]
     wave = np.zeros((len(idx), max(n)), dtype=np.int16)
     lab_len = [len(utts[i][1]) for i in idx]
@@ -82,7 +105,7 @@ def to_device(utts, idx, dev, dtype, augment=None):
         wave[r, :n[r]] = utts[i][0]
         labels[r, :lab_len[r]] = utts[i][1]
     x, frame_lengths = quaternion_fbank(torch.from_numpy(wave).to(dev), torch.tensor(n, dtype=torch.int32), normalize='utterance',
-                                        dtype=dtype, augment=augment)
+                                        dtype=dtype, augment=augment, wave_augment=wave_augment)
     labels = torch.from_numpy(labels).to(dev)
     label_length = torch.tensor(lab_len, dtype=torch.int32, device=dev)[:, None]
     return x, frame_lengths[:, None], labels, label_length
@@ -117,6 +140,11 @@ def main():
     ap.add_argument('--time-masks', type=int, default=2)
     ap.add_argument('--time-width', type=int, default=25, help='largest time mask, frames ...')
     ap.add_argument('--time-ratio', type=float, default=0.2, help='... and at most this share of the utterance')
+    ap.add_argument('--speed-perturb', action='store_true',
+                    help='speed and volume perturbation of the training waveforms (never of evaluation batches); labels are unchanged')
+    ap.add_argument('--speeds', type=parse_speeds, default=((9, 10), (1, 1), (11, 10)),
+                    help='speed perturbation: comma-separated speeds, each taken as a fraction with a denominator <= 32')
+    ap.add_argument('--volume', type=parse_volume, default=(1.0, 1.0), help='speed perturbation: LO,HI of the linear gain drawn per utterance')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
@@ -153,6 +181,9 @@ def main():
     if args.specaug:
         augment = SpecAugment(time_warp=args.time_warp, freq_masks=args.freq_masks, freq_width=args.freq_width, time_masks=args.time_masks,
                               time_width=args.time_width, time_ratio=args.time_ratio, seed=args.seed & 0xFFFFFFFF)
+    wave_augment = None
+    if args.speed_perturb:
+        wave_augment = SpeedPerturb(speeds=args.speeds, gain=args.volume, seed=args.seed & 0xFFFFFFFF)
     # clipping / float16 / dynamic scaling: the guarded step (qcnn_amd.training.GradGuard).  Norm, overflow check, clip and scale
     # update all happen on the device, and so does the step count (a skipped step does not advance it).
     guard = None
@@ -161,7 +192,7 @@ def main():
                           loss_scale=2.0 ** 12 if dtype == torch.float16 or args.dynamic_loss_scale else 1.0)
         step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
     for step in range(1, args.steps + 1):
-        x, il, labels, ll = to_device(train, batches[rng.randint(len(batches))], dev, dtype, augment)
+        x, il, labels, ll = to_device(train, batches[rng.randint(len(batches))], dev, dtype, augment, wave_augment)
         if guard is None:
             loss = model.training_loss(x, labels, il, ll)
             loss.backward()

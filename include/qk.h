@@ -554,6 +554,61 @@ int qk_spec_augment(int32_t in_dtype, int32_t out_dtype, int32_t batch, int32_t 
                     const void *x, const int32_t *lengths, const qk_specaug_t *policy, const uint32_t *counter_dev /* NULL: 0 */,
                     void *out, int32_t *plan /* (batch, 36) or NULL */, void *stream);
 
+/* ---- Speed and volume perturbation ------------------------------------------------------------------------------------------
+ * The waveform augmentation of Ko et al., 2015 ("Audio augmentation for speech recognition"), in front of qk_fbank_quaternion,
+ * as ONE launch: every utterance is resampled by one of the policy's speeds p/q (tempo and pitch change together, as `sox speed`
+ * does: a speed above 1 shortens the utterance) and multiplied by a random linear gain.  wave is a contiguous (batch, max_samples)
+ * matrix of wave_dtype (QK_WAVE_I16 or QK_WAVE_F32, as for the front end), lengths (batch) int32 the valid samples per row; out is
+ * a contiguous (batch, out_samples) fp32 matrix at the input's scale (int16 input stays in [-32768, 32767] times the gain),
+ * out_lengths (batch) int32.  The launch also writes out_lengths and the plan; it does not synchronise, needs no workspace and
+ * uses no atomics.  The draws are the counter-based hash of the SpecAugment section: bit-repeatable from (seed, *counter_dev), and
+ * new on every replay of a captured graph whose counter a device op advances.  Seeds of data-parallel ranks: as for SpecAugment.
+ *
+ * Per utterance b, with n = clamp(lengths[b], 0, max_samples):
+ * Draws: fmix, key, u(b,k) and randint(b,k,m) exactly as in the SpecAugment section, with draw indices k = 64 (the speed) and
+ *   k = 65 (the gain).  i = randint(b,64, n_speeds).  f = float(u(b,65) >> 8) * 2^-24 (exact, in [0, 1)).
+ *   g = gain_lo + (gain_hi - gain_lo) * f in fp32: the difference, the product and the sum are each rounded once (no fused
+ *   multiply-add), so gain_lo == gain_hi gives g = gain_lo exactly.
+ * Length: p = num[i], q = den[i];  n' = ceil(n q / p);  out_lengths[b] = n';  out[b, m] = 0 for n' <= m < out_samples.
+ * p == q:  out[b, m] = g * x[b, m] for m < n', one fp32 product and no filter; with g == 1 the result is a bit copy.
+ * Otherwise, for m < n':  i0 = (m p) / q, r = (m p) % q in integer arithmetic (i0 <= n - 1 always holds);
+ *   acc = sum_{j = -Kw}^{Kw+1} T_i[r][j] * x[b, i0 + j], with x taken as 0 outside [0, n); products and sums are fp32, in any
+ *   order, fused or not;  out[b, m] = g * acc, one more fp32 product.
+ * Nothing from a sample >= n of an input row ever reaches the output, whatever it holds (NaN included).
+ * Filter table: built by the HOST in float64 and rounded once to fp32; the device only forms dot products, and no sinf result is
+ *   part of this contract.  It is the band-limited windowed sinc of torchaudio's sinc_interp_hann with Z zero crossings:
+ *   fc = rolloff * min(1, q / p);  Kw = half_width[i] = ceil(Z / fc);  for r in [0, q) and j in [-Kw, Kw + 1]:
+ *   t = fc * (r / q - j);  T[r][j] = fc * sinc(t) * cos^2(pi t / (2 Z)) for |t| < Z and 0 otherwise;  sinc(t) = sin(pi t) / (pi t),
+ *   sinc(0) = 1.  No per-phase normalisation.  tables + table_offset[i] holds the q phases of speed i, each 2 Kw + 2 consecutive
+ *   floats (j ascending), phase r first float at r (2 Kw + 2).  A speed with num == den has no table (half_width 0; its table_offset
+ *   is not read).  Z = 6 and rolloff = 0.99 give Kw = 7, 16 taps, for 9/10 and 11/10.  tables must be 4-byte aligned.
+ * Plan row (plan: (batch, QK_SPEED_PLAN_WORDS) int32, or NULL): {n, i, n', the bits of g}.
+ * qk_speed_perturb_out_samples: the largest ceil(max_samples q / p) over the policy's speeds -- the width the caller gives `out`,
+ *   known without reading anything from the device; -1 for a NULL or invalid policy or max_samples < 1.
+ * QK_ERR_INVALID_ARG: n_speeds outside 1 .. QK_SPEED_MAX_SPEEDS; a num or den outside 1 .. QK_SPEED_MAX_DEN or a ratio outside
+ *   [1/2, 2]; half_width 0 where num != den, nonzero where num == den, or negative; a negative table_offset; gains not finite,
+ *   negative, or gain_lo > gain_hi; out_samples below qk_speed_perturb_out_samples; out overlapping wave; a wave_dtype other than
+ *   the two; a NULL wave / lengths / policy / out / out_lengths, or NULL tables when a speed has num != den; batch or
+ *   max_samples < 1; pointers not aligned to their element size.
+ * QK_ERR_UNSUPPORTED: 2 Kw + 2 > QK_SPEED_MAX_TAPS; max_samples or out_samples >= 2^26 (below it m p and n q fit 32 bits). */
+#define QK_SPEED_MAX_SPEEDS 8
+#define QK_SPEED_MAX_DEN    32
+#define QK_SPEED_MAX_TAPS   64
+#define QK_SPEED_PLAN_WORDS 4
+typedef struct qk_speed_perturb_t {
+    int32_t n_speeds;                              /* 1 .. QK_SPEED_MAX_SPEEDS */
+    int32_t num[QK_SPEED_MAX_SPEEDS];              /* speed i = num[i] / den[i], both in 1 .. QK_SPEED_MAX_DEN, 1/2 <= num/den <= 2 */
+    int32_t den[QK_SPEED_MAX_SPEEDS];
+    int32_t half_width[QK_SPEED_MAX_SPEEDS];       /* Kw of speed i; 0 when num == den */
+    int32_t table_offset[QK_SPEED_MAX_SPEEDS];     /* first float of speed i's taps in `tables` */
+    float gain_lo, gain_hi;                        /* linear amplitude factor drawn from [gain_lo, gain_hi); lo == hi: constant */
+    uint32_t seed;
+} qk_speed_perturb_t;
+int64_t qk_speed_perturb_out_samples(int64_t max_samples, const qk_speed_perturb_t *policy);
+int qk_speed_perturb(int32_t wave_dtype, int32_t batch, int64_t max_samples, const void *wave, const int32_t *lengths,
+                     const qk_speed_perturb_t *policy, const float *tables /* device */, const uint32_t *counter_dev /* NULL: 0 */,
+                     int64_t out_samples, float *out, int32_t *out_lengths, int32_t *plan /* (batch, 4) or NULL */, void *stream);
+
 /* Softmax over the last axis of a (rows, cols <= 64) matrix, one wave per row -- the activation of the model's
  * TimeDistributed(Dense(62, activation='softmax')) output layer (models/interspeech_model.py:171-175) and its autodiff:
  *   fwd   y = softmax(logits + bias)          logits: fp32 (the GEMM's fp32 output), bias: fp32 or NULL, y: `dtype`

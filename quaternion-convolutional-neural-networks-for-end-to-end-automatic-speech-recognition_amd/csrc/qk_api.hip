@@ -1256,6 +1256,89 @@ int qk_spec_augment(int32_t in_dtype, int32_t out_dtype, int32_t batch, int32_t 
                                             (hipStream_t)stream), "qk_spec_augment");
 }
 
+// 0 when the policy is one qk.h admits, else the error code (message set)
+static int speed_policy_check(const qk_speed_perturb_t *policy)
+{
+    if (!policy) { set_error("speed_perturb: policy is NULL"); return QK_ERR_INVALID_ARG; }
+    const qk_speed_perturb_t &p = *policy;
+    if (p.n_speeds < 1 || p.n_speeds > QK_SPEED_MAX_SPEEDS) {
+        set_error("speed_perturb: n_speeds %d outside 1 .. %d", p.n_speeds, QK_SPEED_MAX_SPEEDS); return QK_ERR_INVALID_ARG;
+    }
+    if (!isfinite(p.gain_lo) || !isfinite(p.gain_hi) || p.gain_lo < 0.f || p.gain_lo > p.gain_hi) {
+        set_error("speed_perturb: gains %g, %g must be finite with 0 <= gain_lo <= gain_hi", (double)p.gain_lo, (double)p.gain_hi);
+        return QK_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < p.n_speeds; ++i) {
+        const int num = p.num[i], den = p.den[i], kw = p.half_width[i];
+        if (num < 1 || num > QK_SPEED_MAX_DEN || den < 1 || den > QK_SPEED_MAX_DEN || 2 * num < den || num > 2 * den) {
+            set_error("speed_perturb: speed %d = %d / %d (both in 1 .. %d, ratio in [1/2, 2])", i, num, den, QK_SPEED_MAX_DEN);
+            return QK_ERR_INVALID_ARG;
+        }
+        if (kw < 0 || (num == den) != (kw == 0)) {
+            set_error("speed_perturb: speed %d = %d / %d with half_width %d (0 exactly when num == den)", i, num, den, kw);
+            return QK_ERR_INVALID_ARG;
+        }
+        if (num != den && p.table_offset[i] < 0) { set_error("speed_perturb: table_offset[%d] = %d", i, p.table_offset[i]); return QK_ERR_INVALID_ARG; }
+    }
+    for (int i = 0; i < p.n_speeds; ++i)
+        if (2 * (long long)p.half_width[i] + 2 > QK_SPEED_MAX_TAPS) {
+            set_error("speed_perturb: speed %d has %lld taps, more than %d", i, 2 * (long long)p.half_width[i] + 2, QK_SPEED_MAX_TAPS);
+            return QK_ERR_UNSUPPORTED;
+        }
+    return 0;
+}
+
+int64_t qk_speed_perturb_out_samples(int64_t max_samples, const qk_speed_perturb_t *policy)
+{
+    if (max_samples < 1) { set_error("speed_perturb_out_samples: max_samples %lld < 1", (long long)max_samples); return -1; }
+    const int rc = speed_policy_check(policy);
+    if (rc != 0 && rc != QK_ERR_UNSUPPORTED) return -1;                    // (the tap limit does not bear on the lengths)
+    if (max_samples > INT64_MAX / QK_SPEED_MAX_DEN) { set_error("speed_perturb_out_samples: max_samples too large"); return -1; }
+    int64_t most = 0;
+    for (int i = 0; i < policy->n_speeds; ++i) {
+        const int64_t len = (max_samples * policy->den[i] + policy->num[i] - 1) / policy->num[i];
+        if (len > most) most = len;
+    }
+    return most;
+}
+
+int qk_speed_perturb(int32_t wave_dtype, int32_t batch, int64_t max_samples, const void *wave, const int32_t *lengths,
+                     const qk_speed_perturb_t *policy, const float *tables, const uint32_t *counter_dev, int64_t out_samples, float *out,
+                     int32_t *out_lengths, int32_t *plan, void *stream)
+{
+    if (batch < 1 || max_samples < 1 || (wave_dtype != QK_WAVE_F32 && wave_dtype != QK_WAVE_I16)) {
+        set_error("speed_perturb: bad arguments (batch %d, max_samples %lld, wave_dtype %d)", batch, (long long)max_samples, wave_dtype);
+        return QK_ERR_INVALID_ARG;
+    }
+    if (!wave || !lengths || !out || !out_lengths) { set_error("speed_perturb: NULL argument"); return QK_ERR_INVALID_ARG; }
+    const int rc = speed_policy_check(policy);
+    if (rc == QK_ERR_INVALID_ARG) return rc;
+    bool filters = false;
+    for (int i = 0; i < policy->n_speeds; ++i) filters |= policy->num[i] != policy->den[i];
+    if (filters && !tables) { set_error("speed_perturb: tables is NULL, but a speed has num != den"); return QK_ERR_INVALID_ARG; }
+    const int64_t limit = (int64_t)1 << 26;
+    if (max_samples < limit && out_samples < qk_speed_perturb_out_samples(max_samples, policy)) {
+        set_error("speed_perturb: out_samples %lld below the %lld that max_samples %lld needs", (long long)out_samples,
+                  (long long)qk_speed_perturb_out_samples(max_samples, policy), (long long)max_samples);
+        return QK_ERR_INVALID_ARG;
+    }
+    const size_t wave_elem = wave_dtype == QK_WAVE_I16 ? 2 : 4;
+    if (!aligned(wave, wave_elem) || !aligned(out, 4) || !aligned(lengths, 4) || !aligned(out_lengths, 4) || (plan && !aligned(plan, 4)) ||
+        (tables && !aligned(tables, 4)) || (counter_dev && !aligned(counter_dev, 4))) {
+        set_error("speed_perturb: pointers must be aligned to their element size"); return QK_ERR_INVALID_ARG;
+    }
+    if (rc != 0) return rc;                                                // the tap limit
+    if (max_samples >= limit || out_samples >= limit) {
+        set_error("speed_perturb: max_samples %lld / out_samples %lld must be below 2^26", (long long)max_samples, (long long)out_samples);
+        return QK_ERR_UNSUPPORTED;
+    }
+    const uintptr_t wa = reinterpret_cast<uintptr_t>(wave), oa = reinterpret_cast<uintptr_t>(out);
+    const size_t wave_bytes = (size_t)batch * (size_t)max_samples * wave_elem, out_bytes = (size_t)batch * (size_t)out_samples * 4;
+    if (wa < oa + out_bytes && oa < wa + wave_bytes) { set_error("speed_perturb: out overlaps wave"); return QK_ERR_INVALID_ARG; }
+    return check_launch(launch_speed_perturb(wave_dtype, batch, (int)max_samples, wave, lengths, *policy, tables, counter_dev, (int)out_samples,
+                                             out, out_lengths, plan, (hipStream_t)stream), "qk_speed_perturb");
+}
+
 int qk_softmax_rows_fwd(int32_t dtype, int64_t rows, int32_t cols, const float *logits, const float *bias, void *y, void *stream)
 {
     if (!logits || !y || rows < 0 || cols < 1 || cols > 64 || dtype < QK_F32 || dtype > QK_F16) { set_error("qk_softmax_rows_fwd: bad argument (1 <= cols <= 64)"); return QK_ERR_INVALID_ARG; }

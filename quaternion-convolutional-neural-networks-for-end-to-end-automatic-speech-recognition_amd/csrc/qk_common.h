@@ -370,6 +370,10 @@ int launch_fbank(int wave_dtype, const void *wave, const int *lengths, const Fba
 // SpecAugment (qk_specaug.hip)
 int launch_spec_augment(int in_dtype, int out_dtype, int B, int P, int R, int T, const void *x, const int *lengths,
                         const qk_specaug_t &pol, const unsigned *counter, void *out, int *plan, hipStream_t stream);
+// speed and volume perturbation (qk_wave_aug.hip)
+int launch_speed_perturb(int wave_dtype, int B, int n_max, const void *wave, const int *lengths, const qk_speed_perturb_t &pol,
+                         const float *tables, const unsigned *counter, int n_out, float *out, int *out_lengths, int *plan,
+                         hipStream_t stream);
 int launch_relayout16(const void *src, void *dst, int n, int A, int B, hipStream_t stream);     // (n, A, B) -> (n, B, A), 16-bit
 struct PoolGeom { int batch, ih, iw, C, wh, ww, oh, ow; };
 int launch_maxpool(int dtype, bool backward, const void *x, const void *dy, void *out, const PoolGeom &g, hipStream_t stream);

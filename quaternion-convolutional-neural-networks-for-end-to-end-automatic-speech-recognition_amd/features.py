@@ -58,7 +58,8 @@ def mel_filterbank(nfilt=40, nfft=512, sample_rate=16000, lowfreq=0, highfreq=No
 
 
 def quaternion_fbank(wave, lengths=None, sample_rate=16000, winlen=0.025, winstep=0.01, nfilt=40, nfft=512, lowfreq=0, highfreq=None,
-                     preemph=0.97, window='rect', delta_n=2, append_energy=True, normalize=None, dtype=torch.float32, augment=None):
+                     preemph=0.97, window='rect', delta_n=2, append_energy=True, normalize=None, dtype=torch.float32, augment=None,
+                     wave_augment=None):
     """Quaternion filter-bank features of a batch of waveforms, on the device.
 
     wave: (B, n_max) or (n_max,) int16 / float32 CUDA tensor; lengths: samples per utterance (B,) (default n_max each; clamped to
@@ -73,7 +74,14 @@ def quaternion_fbank(wave, lengths=None, sample_rate=16000, winlen=0.025, winste
 
     augment: a SpecAugment policy (training batches only).  The features are then computed in float32, after any normalisation,
     augmented with the frame lengths as the utterance lengths, and rounded once to `dtype`; after normalize='utterance' a fill of 0
-    is the per-row mean.  None (the default): no augmentation, the calls are exactly those of the plain front end."""
+    is the per-row mean.  None (the default): no augmentation, the calls are exactly those of the plain front end.
+
+    wave_augment: a SpeedPerturb policy (training batches only).  The waveforms are perturbed first, and the front end runs on the
+    perturbed float32 waveforms and THEIR lengths: T = num_frames of the perturbed batch's width (wider than n_max when the policy has
+    a speed below 1), frame_lengths those of the perturbed utterances.  Labels are unchanged.  It combines with `augment`.  None (the
+    default): the calls are exactly those of the plain front end."""
+    if wave_augment is not None and not isinstance(wave_augment, SpeedPerturb):
+        raise TypeError('quaternion_fbank: wave_augment must be a SpeedPerturb or None, got %r' % (wave_augment,))
     if augment is not None and not isinstance(augment, SpecAugment):
         raise TypeError('quaternion_fbank: augment must be a SpecAugment or None, got %r' % (augment,))
     if window not in WINDOWS:
@@ -112,6 +120,9 @@ def quaternion_fbank(wave, lengths=None, sample_rate=16000, winlen=0.025, winste
         if lengths.numel() != b:
             raise ValueError('quaternion_fbank: lengths must have B = %d entries, got %d' % (b, lengths.numel()))
         lengths = lengths.reshape(-1).to(device=wave.device, dtype=torch.int32)
+    if wave_augment is not None:
+        wave, lengths = wave_augment(wave, lengths)
+        n_max = wave.shape[1]
     bins = _mel_bins(nfilt, nfft, sample_rate, lowfreq, highfreq).astype(np.int64).tolist()
     frames = num_frames(n_max, sample_rate, winlen, winstep)
     if augment is None:
@@ -185,6 +196,72 @@ class SpecAugment(object):
         for name, v in (('seed', seed), ('counter', counter)):
             if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 0xFFFFFFFF:
                 raise ValueError('SpecAugment.load_state_dict: %s must be an integer in [0, 2^32), got %r' % (name, v))
+        self.policy['seed'] = seed
+        if self._counter is None:
+            self._pending = counter
+        else:
+            self._counter.fill_(counter - (1 << 32) if counter >= 1 << 31 else counter)
+
+
+class SpeedPerturb(object):
+    """A speed and volume perturbation policy (Ko et al., 2015) for waveforms, with its own device counter.
+
+        sp = SpeedPerturb(seed=args.seed)
+        x, il = quaternion_fbank(wave, lengths, normalize='utterance', dtype=torch.bfloat16, wave_augment=sp)   # training batches only
+
+    Per utterance: one of `speeds` ((num, den) pairs, default 0.9 / 1.0 / 1.1) is drawn and the utterance resampled by it, which
+    changes tempo and pitch together as `sox speed` does, and a linear gain is drawn from [gain[0], gain[1]) -- one launch
+    (functional.speed_perturb; semantics: include/qk.h, "Speed and volume perturbation").  The labels of an utterance are unchanged;
+    a sped-up utterance has fewer frames for the same labels, so a batch that was just feasible for CTC may stop being so.
+    Nobody has measured a phone error rate with this augmentation here.
+
+    The draws are a hash of (seed, counter, utterance index): bit-repeatable from the seed.  __call__ advances the counter with a
+    device op behind the kernel, so a captured graph draws anew on every replay and nothing is read on the host (call the policy once
+    before capturing: the first call on a device creates the counter and copies the filter tables).
+    Data-parallel ranks must pass DIFFERENT seeds, or every rank perturbs its utterance b like every other's; seed and utterance
+    index enter the hash as a sum, so keep the seeds at least a batch apart (e.g. seed + 65536 * rank).
+    state_dict() / load_state_dict() carry the seed and the counter (reading the counter synchronises)."""
+
+    def __init__(self, speeds=F.DEFAULT_SPEEDS, gain=(1.0, 1.0), zeros=6, rolloff=0.99, seed=0):
+        speeds, gain = F._speed_args('SpeedPerturb', speeds, gain, zeros, rolloff, seed)
+        F.speed_perturb_tables(speeds, zeros, rolloff)          # (refuses a filter with too many taps)
+        self.policy = dict(speeds=speeds, gain=gain, zeros=zeros, rolloff=float(rolloff), seed=seed)
+        self._counter = None            # one int32 on the device of the first call; the kernel reads its 32 bits as unsigned
+        self._pending = 0               # counter value to start from (load_state_dict before the first call)
+        self.last_plan = None
+
+    @property
+    def seed(self):
+        return self.policy['seed']
+
+    def _counter_on(self, device):
+        if self._counter is None:
+            v = self._pending - (1 << 32) if self._pending >= 1 << 31 else self._pending
+            self._counter = torch.full((1,), v, dtype=torch.int32, device=device)
+        elif self._counter.device != device:
+            raise ValueError('SpeedPerturb: this policy\'s counter lives on %s, the input on %s' % (self._counter.device, device))
+        return self._counter
+
+    def __call__(self, wave, lengths):
+        """(out, out_lengths) of functional.speed_perturb for wave (B, n_max); the plan of the call is kept in .last_plan."""
+        if not torch.is_tensor(wave) or not wave.is_cuda:
+            raise RuntimeError('SpeedPerturb: got a CPU tensor. Speed perturbation runs only on the MI355X HIP path (libqk_hip.so); '
+                               'there is no CPU fallback.')
+        counter = self._counter_on(wave.device)
+        out, out_lengths, self.last_plan = F.speed_perturb(wave, lengths, counter=counter, return_plan=True, **self.policy)
+        counter.add_(1)                 # wraps mod 2^32, like the kernel's key
+        return out, out_lengths
+
+    def state_dict(self):
+        counter = self._pending if self._counter is None else int(self._counter.item()) & 0xFFFFFFFF
+        return {'seed': self.policy['seed'], 'counter': counter}
+
+    def load_state_dict(self, d):
+        """Takes what state_dict() gave; checked on the host before anything is written."""
+        seed, counter = d['seed'], d['counter']
+        for name, v in (('seed', seed), ('counter', counter)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError('SpeedPerturb.load_state_dict: %s must be an integer in [0, 2^32), got %r' % (name, v))
         self.policy['seed'] = seed
         if self._counter is None:
             self._pending = counter

@@ -12,6 +12,7 @@ a CPU tensor or a missing libqk_hip.so raises.
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1567,3 +1568,151 @@ def spec_augment(x, lengths, *, time_warp=0, freq_masks=0, freq_width=0, time_ma
                                      _ptr(counter), _ptr(out), _ptr(plan), _stream(x))
     L.check(rc, 'qk_spec_augment')
     return (out, plan) if return_plan else out
+
+
+# ---- Speed and volume perturbation (include/qk.h, "Speed and volume perturbation") ---------------------------------------------
+DEFAULT_SPEEDS = ((9, 10), (1, 1), (11, 10))
+_speed_tables_host = {}         # (speeds, zeros, rolloff) -> speed_perturb_tables' dict
+_speed_tables_dev = {}          # (speeds, zeros, rolloff, device) -> the float32 tables on that device
+
+
+def _speed_args(what, speeds, gain, zeros, rolloff, seed):
+    """The checked (speeds as a tuple of int pairs, (gain_lo, gain_hi)); ValueError / TypeError on the host, before any device is
+    touched."""
+    try:
+        speeds = tuple(tuple(s) for s in speeds)
+    except TypeError:
+        raise TypeError('%s: speeds must be a sequence of (num, den) pairs, got %r' % (what, speeds))
+    if not 1 <= len(speeds) <= L.QK_SPEED_MAX_SPEEDS:
+        raise ValueError('%s: between 1 and %d speeds, got %d' % (what, L.QK_SPEED_MAX_SPEEDS, len(speeds)))
+    for s in speeds:
+        if len(s) != 2:
+            raise ValueError('%s: a speed is a (num, den) pair, got %r' % (what, s))
+        for v in s:
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError('%s: a speed is a pair of integers, got %r (write 0.9 as (9, 10))' % (what, s))
+        num, den = s
+        if not (1 <= num <= L.QK_SPEED_MAX_DEN and 1 <= den <= L.QK_SPEED_MAX_DEN and den <= 2 * num and num <= 2 * den):
+            raise ValueError('%s: speed %d / %d: both must lie in 1 .. %d and the ratio in [1/2, 2]' % (what, num, den, L.QK_SPEED_MAX_DEN))
+    try:
+        lo, hi = gain
+    except (TypeError, ValueError):
+        raise ValueError('%s: gain must be a (low, high) pair, got %r' % (what, gain))
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError('%s: the gains must be finite numbers, got %r' % (what, gain))
+    if not 0.0 <= lo <= hi or hi > 3e38:
+        raise ValueError('%s: need 0 <= gain low <= gain high (float32), got %r' % (what, gain))
+    if isinstance(zeros, bool) or not isinstance(zeros, int):
+        raise TypeError('%s: zeros must be an integer, got %r' % (what, zeros))
+    if zeros < 1:
+        raise ValueError('%s: zeros must be >= 1, got %d' % (what, zeros))
+    if isinstance(rolloff, bool) or not isinstance(rolloff, (int, float)) or not math.isfinite(rolloff) or not 0.0 < rolloff <= 1.0:
+        raise ValueError('%s: rolloff must lie in (0, 1], got %r' % (what, rolloff))
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError('%s: seed must be an integer, got %r' % (what, seed))
+    if not 0 <= seed <= 0xFFFFFFFF:
+        raise ValueError('%s: seed must fit 32 unsigned bits, got %d' % (what, seed))
+    return speeds, (float(lo), float(hi))
+
+
+def speed_perturb_tables(speeds=DEFAULT_SPEEDS, zeros=6, rolloff=0.99):
+    """The polyphase filter tables of a set of speeds, built on the host (include/qk.h, "Filter table": torchaudio's
+    sinc_interp_hann, float64, rounded once to float32), and the policy fields that go with them.  Returns a dict: num, den,
+    half_width, table_offset (lists, one entry per speed; half_width 0 and no table where num == den) and tables, one float32
+    NumPy array that holds speed i's (den, 2 half_width + 2) matrix from table_offset[i] on.  Cached per (speeds, zeros, rolloff);
+    speed_perturb keeps one device copy per device."""
+    speeds, _ = _speed_args('speed_perturb_tables', speeds, (1.0, 1.0), zeros, rolloff, 0)
+    key = (speeds, zeros, float(rolloff))
+    hit = _speed_tables_host.get(key)
+    if hit is not None:
+        return hit
+    half_width, offsets, parts, at = [], [], [], 0
+    for p, q in speeds:
+        if p == q:
+            half_width.append(0)
+            offsets.append(0)
+            continue
+        fc = float(rolloff) * min(1.0, q / p)
+        kw = int(math.ceil(zeros / fc))
+        if 2 * kw + 2 > L.QK_SPEED_MAX_TAPS:
+            raise ValueError('speed_perturb_tables: speed %d / %d with zeros %d and rolloff %r needs %d taps, more than %d'
+                             % (p, q, zeros, rolloff, 2 * kw + 2, L.QK_SPEED_MAX_TAPS))
+        r = np.arange(q, dtype=np.float64)[:, None]
+        j = np.arange(-kw, kw + 2, dtype=np.float64)[None, :]
+        t = fc * (r / q - j)
+        tab = np.where(np.abs(t) < zeros, fc * np.sinc(t) * np.cos(np.pi * t / (2.0 * zeros)) ** 2, 0.0)
+        half_width.append(kw)
+        offsets.append(at)
+        parts.append(tab.astype(np.float32).reshape(-1))
+        at += tab.size
+    tables = np.concatenate(parts) if parts else np.zeros(0, dtype=np.float32)
+    tables.setflags(write=False)
+    hit = dict(num=[s[0] for s in speeds], den=[s[1] for s in speeds], half_width=half_width, table_offset=offsets, tables=tables)
+    _speed_tables_host[key] = hit
+    return hit
+
+
+def _speed_policy(speeds, gain, zeros, rolloff, seed):
+    """(qk_speed_perturb_t, host tables dict, cache key) of checked arguments."""
+    tab = speed_perturb_tables(speeds, zeros, rolloff)
+    pol = L.SpeedPerturbPolicy()
+    pol.n_speeds = len(speeds)
+    for i in range(len(speeds)):
+        pol.num[i], pol.den[i], pol.half_width[i], pol.table_offset[i] = tab['num'][i], tab['den'][i], tab['half_width'][i], tab['table_offset'][i]
+    pol.gain_lo, pol.gain_hi, pol.seed = gain[0], gain[1], seed
+    return pol, tab, (speeds, zeros, float(rolloff))
+
+
+def speed_perturb(wave, lengths, *, speeds=DEFAULT_SPEEDS, gain=(1.0, 1.0), zeros=6, rolloff=0.99, seed=0, counter=None,
+                  return_plan=False):
+    """Speed and volume perturbation of a batch of waveforms as one launch (qk_speed_perturb; semantics: include/qk.h, "Speed and
+    volume perturbation").
+
+    wave (B, n_max) int16 / float32 on the device; lengths (B,) valid samples per utterance (clamped to [0, n_max]).  Per utterance
+    one of `speeds` ((num, den) pairs: 0.9 is (9, 10)) is drawn and the utterance resampled by it with a windowed-sinc filter of
+    `zeros` zero crossings (tempo and pitch change together, as `sox speed` does; speed 11/10 leaves ceil(10 n / 11) samples), and a
+    linear gain is drawn from [gain[0], gain[1]).  The draws are a hash of (seed, counter, utterance): equal arguments give equal
+    bits.  counter: one-element int32 / uint32 DEVICE tensor read by the kernel (None: 0).
+
+    Returns (out, out_lengths): out (B, ceil(n_max / slowest speed)) float32 at the input's scale, zero from out_lengths[b] on;
+    out_lengths (B,) int32 on the device.  With return_plan also plan (B, 4) int32 = {n, speed index, n', bits of the gain}.  No
+    host sync; the filter tables are built on the host once per (speeds, zeros, rolloff) and copied once per device."""
+    what = 'speed_perturb'
+    speeds, gain = _speed_args(what, speeds, gain, zeros, rolloff, seed)
+    pol, tab, key = _speed_policy(speeds, gain, zeros, rolloff, seed)
+    if torch.is_tensor(wave) and wave.dtype not in (torch.int16, torch.float32):
+        raise TypeError('%s: waveforms must be int16 or float32, got %s' % (what, wave.dtype))
+    if not torch.is_tensor(wave) or not wave.is_cuda:
+        raise RuntimeError('%s: got a CPU tensor. Speed perturbation runs only on the MI355X HIP path (libqk_hip.so); there is no CPU '
+                           'fallback.' % what)
+    if wave.dim() != 2 or min(wave.shape) < 1:
+        raise ValueError('%s: wave must be a non-empty (B, samples) tensor, got shape %s' % (what, tuple(wave.shape)))
+    b, n_max = wave.shape
+    lengths = lengths if torch.is_tensor(lengths) else torch.as_tensor(lengths)
+    if lengths.numel() != b:
+        raise ValueError('%s: lengths must have B = %d entries, got %d' % (what, b, lengths.numel()))
+    lengths = lengths.reshape(-1).to(device=wave.device, dtype=torch.int32).contiguous()
+    if counter is not None:
+        if (not torch.is_tensor(counter) or counter.device != wave.device or counter.numel() != 1
+                or counter.dtype not in (torch.int32, torch.uint32)):
+            raise ValueError('%s: counter must be a one-element int32 / uint32 tensor on %s' % (what, wave.device))
+    n_out = int(L.lib().qk_speed_perturb_out_samples(n_max, ctypes.byref(pol)))
+    if n_out < 1 or max(n_max, n_out) >= 1 << 26:
+        raise ValueError('%s: rows of %d samples (%d after the slowest speed) are not supported (limit 2^26)' % (what, n_max, n_out))
+    tables = None
+    if tab['tables'].size:
+        tables = _speed_tables_dev.get(key + (wave.device,))
+        if tables is None:
+            tables = torch.from_numpy(tab['tables'].copy()).to(wave.device)
+            _speed_tables_dev[key + (wave.device,)] = tables
+    wave = wave.contiguous()
+    out = torch.empty((b, n_out), dtype=torch.float32, device=wave.device)
+    out_lengths = torch.empty(b, dtype=torch.int32, device=wave.device)
+    plan = torch.empty((b, L.QK_SPEED_PLAN_WORDS), dtype=torch.int32, device=wave.device) if return_plan else None
+    wd = L.QK_WAVE_I16 if wave.dtype == torch.int16 else L.QK_WAVE_F32
+    with _on_device(wave.device):
+        rc = L.lib().qk_speed_perturb(wd, b, n_max, _ptr(wave), _ptr(lengths), ctypes.byref(pol), _ptr(tables), _ptr(counter), n_out,
+                                      _ptr(out), _ptr(out_lengths), _ptr(plan), _stream(wave))
+    L.check(rc, 'qk_speed_perturb')
+    return (out, out_lengths, plan) if return_plan else (out, out_lengths)
