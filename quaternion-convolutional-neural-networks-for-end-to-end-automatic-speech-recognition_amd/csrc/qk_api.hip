@@ -322,77 +322,102 @@ int x_to_first(const qk_conv_desc_t *d, const void *src, void *dst, hipStream_t 
 int y_to_last(const qk_conv_desc_t *d, const void *src, void *dst, hipStream_t s) { return launch_relayout16(src, dst, d->batch, 4 * d->fq, out_positions(d), s); }
 int y_to_first(const qk_conv_desc_t *d, const void *src, void *dst, hipStream_t s) { return launch_relayout16(src, dst, d->batch, out_positions(d), 4 * d->fq, s); }
 
-void prep_geom(const qk_conv_desc_t *d, bool bwd, GemmGeom *gp);
-
-size_t ws_bytes_impl(const qk_conv_desc_t *d, int op)
+// Every descriptor-derived field of the implicit-GEMM geometry (GemmGeom, qk_common.h) of a forward or a backward-data call.
+// The one place that knows them: the calls, qk_conv_fold_taps, the workspace size and qk_conv_prep_kernels all start here, so what
+// small16_shape / band_geom decide about the LAYOUT of a cached workspace is decided on the fields the call itself dispatches on
+// (neither reads sign_tbl, w_prepped or w_ch_major).  Call-specific fields -- relu, has_bias, has_mask, the post-op, ep_mask,
+// w_swapped -- stay zero for the caller to set.
+GemmGeom make_geom(const qk_conv_desc_t *d, bool bwd)
 {
-    if (cf16_ok(d)) {
-        // [what the channels_last call needs][re-laid-out operands]: fwd x, y (+ pre of a post-op); bwd-data dy, y, dx,
-        // dx mask; bwd-weight x, dy, y; fused bwd x, dy, y, dx (+ x_pre of a post-op) -- and never less than its parts
-        const qk_conv_desc_t c = as_ch_last(d);
-        const size_t X = x_bytes16(d), Y = y_bytes16(d);
-        const size_t fwd = align256(ws_bytes_impl(&c, QK_OP_FWD)) + X + 2 * Y;
-        const size_t bd = align256(ws_bytes_impl(&c, QK_OP_BWD_DATA)) + 2 * Y + 2 * X;
-        const size_t bw = align256(ws_bytes_impl(&c, QK_OP_BWD_WEIGHT)) + X + 2 * Y;
-        const size_t bb = align256(ws_bytes_impl(&c, QK_OP_BWD)) + 2 * X + 2 * Y;
-        switch (op) {
-        case QK_OP_FWD: return fwd;
-        case QK_OP_BWD_DATA: return bd;
-        case QK_OP_BWD_WEIGHT: return bw;
-        case QK_OP_BWD: { size_t m = bb; if (bd > m) m = bd; if (bw > m) m = bw; return m; }
-        }
-        return 0;
+    GemmGeom g;
+    memset(&g, 0, sizeof(g));
+    const Strides xs = act_strides(d->in_spatial, 4 * d->cq, d->layout);
+    const Strides ys = act_strides(d->out_spatial, 4 * d->fq, d->layout);
+    const Strides &in = bwd ? ys : xs, &out = bwd ? xs : ys;               // backward-data gathers dy and produces dx
+    const int32_t *isp = bwd ? d->out_spatial : d->in_spatial, *osp = bwd ? d->in_spatial : d->out_spatial;
+    g.batch = d->batch;
+    g.M = d->batch * osp[0] * osp[1] * osp[2];
+    g.Q = bwd ? d->fq : d->cq; g.J = bwd ? d->cq : d->fq; g.taps = taps_of(d);
+    for (int i = 0; i < 3; ++i) {
+        g.osp[i] = osp[i]; g.isp[i] = isp[i]; g.ks[i] = d->kernel[i];
+        if (!bwd) { g.pa[i] = d->stride[i]; g.pb[i] = d->dilation[i]; g.pc[i] = -d->pad_lo[i]; g.pd[i] = 1; }
+        else { g.pa[i] = 1; g.pb[i] = -d->dilation[i]; g.pc[i] = d->pad_lo[i]; g.pd[i] = d->stride[i]; }      // the position map inverted
+        g.in_ss[i] = in.ss[i];
     }
-    // 16-bit fast path (fwd / bwd-data): 16-bit re-laid-out copy of the compact kernel (+ zero line);
-    // the fp32-MFMA kernels read the compact kernel in place and need nothing
-    // fused backward additionally: the relu-masked copy of dy that bwd-weight writes for bwd-data
-    size_t n = 0;
+    g.in_sn = in.sn; g.in_sc = in.sc;
+    g.out_sn = out.sn; g.out_ss = out.flat_ss; g.out_sc = out.sc;
+    g.sign_tbl = (d->conj != 0) == bwd ? kSignConv : kSignConj;            // backward-data: the transposed table
+    g.w_prepped = d->ws_has_kernel ? 1 : 0;
+    g.w_ch_major = d->kernel_order == QK_KERNEL_CHANNEL_MAJOR;
+    return g;
+}
+
+// The workspace of one operation of a descriptor that the channels_last kernels serve:
+//   [band-layout 16-bit image of the kernel + zero line][fragment layout of k_hconv16_small][relu-masked dy]
+// 16-bit forward / backward-data read the first region (the fp32-MFMA kernels read the compact kernel in place and need nothing);
+// 16 / 32-channel layers keep the small-channel kernel's layout in a second region behind it (go16 finds it at `band`); the fused
+// backward of a relu layer adds the masked copy of dy that backward-weight writes for backward-data.
+struct KernelWs {
+    size_t band;        // first region
+    size_t small;       // second region (0: the shape has none), at offset `band`
+    Small16 sm;         // its geometry (small != 0)
+    size_t dym;         // offset of the masked dy (QK_OP_BWD of a relu layer)
+    size_t total;
+};
+KernelWs kernel_ws(const qk_conv_desc_t *d, int op)
+{
+    KernelWs k;
+    memset(&k, 0, sizeof(k));
     const bool bwd_data = op == QK_OP_BWD_DATA || op == QK_OP_BWD;
     if (d->dtype != QK_F32 && (op == QK_OP_FWD || bwd_data)) {
         // channel counts that are multiples of 16: zero-padded to the kernels' 32-channel granule (other counts never reach the
         // 16-bit kernels; their figure is what it always was)
         const bool on16 = d->cq % 16 == 0 && d->fq % 16 == 0;
-        n += (on16 ? (size_t)taps_of(d) * pad32(d->cq) * 4 * pad32(d->fq) : w_floats(d)) * 2 + 256;
-        if (on16 && d->layout == QK_CH_LAST) {        // 16 / 32-channel layers: the fragment layout of k_hconv16_small in a second region (go16)
-            GemmGeom sg, sbg;
-            Small16 sm;
-            prep_geom(d, bwd_data, &sg);
-            if (d->kernel_order != QK_KERNEL_CHANNEL_MAJOR && small16_shape(sg, &sbg, &sm)) n += small16_region_bytes(sm);
-        }
+        k.band = on16 ? band_image_bytes(taps_of(d), pad32(d->cq), pad32(d->fq)) : w_floats(d) * 2 + 256;
+        GemmGeom bg;
+        if (on16 && d->layout == QK_CH_LAST && d->kernel_order != QK_KERNEL_CHANNEL_MAJOR && small16_shape(make_geom(d, bwd_data), &bg, &k.sm))
+            k.small = small16_region_bytes(k.sm);
     }
-    if (op == QK_OP_BWD && d->activation == QK_ACT_RELU) n = (n + 255) / 256 * 256 + dy_bytes(d);
-    return n;
+    k.total = k.band + k.small;
+    if (op == QK_OP_BWD && d->activation == QK_ACT_RELU) { k.dym = align256(k.total); k.total = k.dym + dy_bytes(d); }
+    return k;
 }
 
-// The geometry fields small16_shape / band_geom look at, filled as conv_fwd_impl / conv_bwd_data_impl fill them (channels_last)
-void prep_geom(const qk_conv_desc_t *d, bool bwd, GemmGeom *gp)
+// The workspace of one operation of a cf16_ok descriptor: [what the channels_last call needs: `base` bytes][one slot per operand
+// re-laid out to channels_last].  Forward: x, y, pre (of a PReLU post-op); backward-data: dy, y, dx, the dx mask / x_pre;
+// backward-weight: x, dy, y (its channels_last call takes no workspace: base is 0 and the slots start the buffer); fused
+// backward: x, dx, dy, y -- reported as never less than the backward-data and backward-weight figures, which the un-fused forms
+// of that call (a linear layer, qk_conv_bwd_post) run in the same buffer.
+struct CfPlan {
+    size_t base;
+    size_t x, dx, dy, y, pre;       // slot offsets (those the operation uses), in the order listed above
+    size_t used;                    // end of the slots (a call that leaves its LAST slot unused -- forward: pre, backward-weight: y -- needs the buffer up to that slot only)
+    size_t total;                   // what qk_*_workspace_bytes reports
+};
+CfPlan cf_plan(const qk_conv_desc_t *d, int op)
 {
-    GemmGeom &g = *gp;
-    memset(&g, 0, sizeof(g));
-    const Strides xs = act_strides(d->in_spatial, 4 * d->cq, d->layout);
-    const Strides ys = act_strides(d->out_spatial, 4 * d->fq, d->layout);
-    g.batch = d->batch;
-    g.taps = taps_of(d);
-    if (!bwd) {
-        g.M = d->batch * d->out_spatial[0] * d->out_spatial[1] * d->out_spatial[2];
-        g.Q = d->cq; g.J = d->fq;
-        for (int i = 0; i < 3; ++i) {
-            g.osp[i] = d->out_spatial[i]; g.isp[i] = d->in_spatial[i]; g.ks[i] = d->kernel[i];
-            g.pa[i] = d->stride[i]; g.pb[i] = d->dilation[i]; g.pc[i] = -d->pad_lo[i]; g.pd[i] = 1;
-            g.in_ss[i] = xs.ss[i];
-        }
-        g.in_sn = xs.sn; g.in_sc = xs.sc; g.out_sn = ys.sn; g.out_ss = ys.flat_ss; g.out_sc = ys.sc;
-    } else {
-        g.M = d->batch * d->in_spatial[0] * d->in_spatial[1] * d->in_spatial[2];
-        g.Q = d->fq; g.J = d->cq;
-        for (int i = 0; i < 3; ++i) {
-            g.osp[i] = d->in_spatial[i]; g.isp[i] = d->out_spatial[i]; g.ks[i] = d->kernel[i];
-            g.pa[i] = 1; g.pb[i] = -d->dilation[i]; g.pc[i] = d->pad_lo[i]; g.pd[i] = d->stride[i];
-            g.in_ss[i] = ys.ss[i];
-        }
-        g.in_sn = ys.sn; g.in_sc = ys.sc; g.out_sn = xs.sn; g.out_ss = xs.flat_ss; g.out_sc = xs.sc;
+    const qk_conv_desc_t c = as_ch_last(d);
+    const size_t X = x_bytes16(d), Y = y_bytes16(d);
+    CfPlan p;
+    memset(&p, 0, sizeof(p));
+    size_t at = p.base = align256(kernel_ws(&c, op).total);
+    auto slot = [&at](size_t bytes) { const size_t o = at; at += bytes; return o; };
+    switch (op) {
+    case QK_OP_FWD: p.x = slot(X); p.y = slot(Y); p.pre = slot(Y); break;
+    case QK_OP_BWD_DATA: p.dy = slot(Y); p.y = slot(Y); p.dx = slot(X); p.pre = slot(X); break;
+    case QK_OP_BWD_WEIGHT: p.x = slot(X); p.dy = slot(Y); p.y = slot(Y); break;
+    case QK_OP_BWD: p.x = slot(X); p.dx = slot(X); p.dy = slot(Y); p.y = slot(Y); break;
     }
+    p.used = p.total = at;
+    if (op == QK_OP_BWD) {
+        const size_t bd = cf_plan(d, QK_OP_BWD_DATA).total, bw = cf_plan(d, QK_OP_BWD_WEIGHT).total;
+        if (bd > p.total) p.total = bd;
+        if (bw > p.total) p.total = bw;
+    }
+    return p;
 }
+
+size_t ws_bytes_impl(const qk_conv_desc_t *d, int op) { return cf16_ok(d) ? cf_plan(d, op).total : kernel_ws(d, op).total; }
 
 int conv_fwd_impl(const qk_conv_desc_t *d, const void *x, const float *w, const float *bias, void *y,
                   void *ws, size_t wsb, hipStream_t stream, const PostOp *post = nullptr, void *pre = nullptr)
@@ -402,37 +427,20 @@ int conv_fwd_impl(const qk_conv_desc_t *d, const void *x, const float *w, const 
     ProfScope prof_scope(QK_OP_FWD, d, stream);
     if (cf16_ok(d)) {
         const qk_conv_desc_t c = as_ch_last(d);
-        const size_t base = align256(ws_bytes_impl(&c, QK_OP_FWD)), X = x_bytes16(d), Y = y_bytes16(d);
+        const CfPlan p = cf_plan(d, QK_OP_FWD);
         const bool two = post && post->kind == 1;
-        if (ws && aligned(ws, 16) && wsb >= base + X + Y + (two ? Y : 0)) {
-            char *p = static_cast<char *>(ws) + base;
-            void *xt = p, *yt = p + X, *pt = two ? p + X + Y : nullptr;
+        if (ws && aligned(ws, 16) && wsb >= (two ? p.used : p.pre)) {
+            char *b = static_cast<char *>(ws);
+            void *xt = b + p.x, *yt = b + p.y, *pt = two ? b + p.pre : nullptr;
             if (int rc = x_to_last(d, x, xt, stream)) return rc;
-            if (int rc = conv_fwd_impl(&c, xt, w, bias, yt, ws, base, stream, post, pt)) return rc;
+            if (int rc = conv_fwd_impl(&c, xt, w, bias, yt, ws, p.base, stream, post, pt)) return rc;
             if (int rc = y_to_first(d, yt, y, stream)) return rc;
             return two ? y_to_first(d, pt, pre, stream) : 0;
         }
     }
-    GemmGeom g;
-    memset(&g, 0, sizeof(g));
-    const Strides xs = act_strides(d->in_spatial, 4 * d->cq, d->layout);
-    const Strides ys = act_strides(d->out_spatial, 4 * d->fq, d->layout);
-    g.batch = d->batch;
-    g.M = d->batch * d->out_spatial[0] * d->out_spatial[1] * d->out_spatial[2];
-    g.Q = d->cq; g.J = d->fq; g.taps = taps_of(d);
-    for (int i = 0; i < 3; ++i) {
-        g.osp[i] = d->out_spatial[i]; g.isp[i] = d->in_spatial[i]; g.ks[i] = d->kernel[i];
-        g.pa[i] = d->stride[i]; g.pb[i] = d->dilation[i]; g.pc[i] = -d->pad_lo[i]; g.pd[i] = 1;
-        g.in_ss[i] = xs.ss[i];
-    }
-    g.in_sn = xs.sn; g.in_sc = xs.sc;
-    g.out_sn = ys.sn; g.out_ss = ys.flat_ss; g.out_sc = ys.sc;
-    g.sign_tbl = d->conj ? kSignConj : kSignConv;
+    GemmGeom g = make_geom(d, false);
     g.relu = d->activation == QK_ACT_RELU;
     g.has_bias = d->has_bias ? 1 : 0;
-    g.has_mask = 0;
-    g.w_prepped = d->ws_has_kernel ? 1 : 0;
-    g.w_ch_major = d->kernel_order == QK_KERNEL_CHANNEL_MAJOR;
     const bool with_post = post && post->kind;
     if (d->dtype != QK_F32) {
         if (with_post && d->layout == QK_CH_LAST && aligned(pre, 16) && aligned(y, 16) &&
@@ -472,34 +480,19 @@ int conv_bwd_data_impl(const qk_conv_desc_t *d, const void *dy, const void *y, c
     if (need && !aligned(ws, 16)) { set_error("workspace must be 16-byte aligned"); return QK_ERR_WORKSPACE; }
     ProfScope prof_scope(QK_OP_BWD_DATA, d, stream);
     if (cf16_ok(d)) {
+        // (`need` above is this plan's total: every slot fits)
         const qk_conv_desc_t c = as_ch_last(d);
-        const size_t base = align256(ws_bytes_impl(&c, QK_OP_BWD_DATA)), X = x_bytes16(d), Y = y_bytes16(d);
-        char *p = static_cast<char *>(ws) + base;
-        void *dyt = p, *yt = mask ? p + Y : nullptr, *dxt = p + 2 * Y, *mt = dx_mask ? p + 2 * Y + X : nullptr;
+        const CfPlan p = cf_plan(d, QK_OP_BWD_DATA);
+        char *b = static_cast<char *>(ws);
+        void *dyt = b + p.dy, *yt = mask ? b + p.y : nullptr, *dxt = b + p.dx, *mt = dx_mask ? b + p.pre : nullptr;
         if (int rc = y_to_last(d, dy, dyt, stream)) return rc;
         if (mask) if (int rc = y_to_last(d, y, yt, stream)) return rc;
         if (dx_mask) if (int rc = x_to_last(d, dx_mask, mt, stream)) return rc;
-        if (int rc = conv_bwd_data_impl(&c, dyt, yt, w, dxt, ws, base, stream, mt, post, dalpha)) return rc;
+        if (int rc = conv_bwd_data_impl(&c, dyt, yt, w, dxt, ws, p.base, stream, mt, post, dalpha)) return rc;
         return x_to_first(d, dxt, dx, stream);
     }
-    GemmGeom g;
-    memset(&g, 0, sizeof(g));
-    const Strides dys = act_strides(d->out_spatial, 4 * d->fq, d->layout);
-    const Strides dxs = act_strides(d->in_spatial, 4 * d->cq, d->layout);
-    g.batch = d->batch;
-    g.M = d->batch * d->in_spatial[0] * d->in_spatial[1] * d->in_spatial[2];
-    g.Q = d->fq; g.J = d->cq; g.taps = taps_of(d);
-    for (int i = 0; i < 3; ++i) {
-        g.osp[i] = d->in_spatial[i]; g.isp[i] = d->out_spatial[i]; g.ks[i] = d->kernel[i];
-        g.pa[i] = 1; g.pb[i] = -d->dilation[i]; g.pc[i] = d->pad_lo[i]; g.pd[i] = d->stride[i];
-        g.in_ss[i] = dys.ss[i];
-    }
-    g.in_sn = dys.sn; g.in_sc = dys.sc;
-    g.out_sn = dxs.sn; g.out_ss = dxs.flat_ss; g.out_sc = dxs.sc;
-    g.sign_tbl = d->conj ? kSignConv : kSignConj;   // transposed table
-    g.relu = 0; g.has_bias = 0; g.has_mask = mask ? 1 : 0;
-    g.w_prepped = d->ws_has_kernel ? 1 : 0;
-    g.w_ch_major = d->kernel_order == QK_KERNEL_CHANNEL_MAJOR;
+    GemmGeom g = make_geom(d, true);
+    g.has_mask = mask ? 1 : 0;
     if (d->dtype != QK_F32) {
         // the 16-bit kernels apply an epilogue mask themselves (needs 16-byte aligned rows of dx_mask)
         g.ep_mask = (dx_mask && aligned(dx_mask, 16)) ? dx_mask : nullptr;
@@ -543,10 +536,10 @@ int conv_bwd_weight_impl(const qk_conv_desc_t *d, const void *x, const void *dy,
     if (cf16_ok(d)) {
         // (ws, wsb): the caller's workspace, used for the re-layout; no masked dy is left behind in this mode
         const qk_conv_desc_t c = as_ch_last(d);
-        const size_t X = x_bytes16(d), Y = y_bytes16(d);
-        if (ws && aligned(ws, 16) && wsb >= X + Y + (mask ? Y : 0)) {
-            char *p = static_cast<char *>(ws);
-            void *xt = p, *dyt = p + X, *yt = mask ? p + X + Y : nullptr;
+        const CfPlan p = cf_plan(d, QK_OP_BWD_WEIGHT);
+        if (ws && aligned(ws, 16) && wsb >= (mask ? p.used : p.y)) {
+            char *b = static_cast<char *>(ws);
+            void *xt = b + p.x, *dyt = b + p.dy, *yt = mask ? b + p.y : nullptr;
             if (int rc = x_to_last(d, x, xt, stream)) return rc;
             if (int rc = y_to_last(d, dy, dyt, stream)) return rc;
             if (mask) if (int rc = y_to_last(d, y, yt, stream)) return rc;
@@ -611,17 +604,17 @@ int conv_bwd_impl(const qk_conv_desc_t *d, const void *x, const void *dy, const 
     if (cf16_ok(d)) {
         // one re-layout of x, dy (and y) serves both gradient kernels; dx goes back once
         const qk_conv_desc_t c = as_ch_last(d);
-        const size_t base = align256(ws_bytes_impl(&c, QK_OP_BWD)), X = x_bytes16(d), Y = y_bytes16(d);
+        const CfPlan p = cf_plan(d, QK_OP_BWD);
         const bool need_y = d->activation == QK_ACT_RELU && !(flags & QK_BWD_DY_PREMASKED);
         if (need_y && !y) { set_error("activation is RELU: the forward output y is required"); return QK_ERR_INVALID_ARG; }
         if (!x || !dy) { set_error("x/dy must not be NULL"); return QK_ERR_INVALID_ARG; }
-        if (ws && aligned(ws, 16) && wsb >= base + 2 * X + 2 * Y) {
-            char *p = static_cast<char *>(ws) + base;
-            void *xt = p, *dxt = p + X, *dyt = p + 2 * X, *yt = need_y ? p + 2 * X + Y : nullptr;
+        if (ws && aligned(ws, 16) && wsb >= p.used) {
+            char *b = static_cast<char *>(ws);
+            void *xt = b + p.x, *dxt = b + p.dx, *dyt = b + p.dy, *yt = need_y ? b + p.y : nullptr;
             if (int rc = x_to_last(d, x, xt, stream)) return rc;
             if (int rc = y_to_last(d, dy, dyt, stream)) return rc;
             if (need_y) if (int rc = y_to_last(d, y, yt, stream)) return rc;
-            if (int rc = conv_bwd_impl(&c, xt, dyt, yt, w, dxt, dw, dbias, ws, base, stream, flags)) return rc;
+            if (int rc = conv_bwd_impl(&c, xt, dyt, yt, w, dxt, dw, dbias, ws, p.base, stream, flags)) return rc;
             return x_to_first(d, dxt, dx, stream);
         }
     }
@@ -639,17 +632,18 @@ int conv_bwd_impl(const qk_conv_desc_t *d, const void *x, const void *dy, const 
     }
     const size_t need = ws_bytes_impl(d, QK_OP_BWD);
     if (need && (!ws || wsb < need)) { set_error("bwd needs %zu workspace bytes, got %zu", need, wsb); return QK_ERR_WORKSPACE; }
-    void *dym = static_cast<char *>(ws) + (bd + 255) / 256 * 256;
-    if ((bd + 255) / 256 * 256 + dy_bytes(d) > wsb + 255) { set_error("workspace too small for the masked dy"); return QK_ERR_WORKSPACE; }
+    void *dym = static_cast<char *>(ws) + kernel_ws(d, QK_OP_BWD).dym;        // (inside the `need` bytes just checked)
     if (int rc = conv_bwd_weight_impl(d, x, dy, y, dw, dbias, dym, stream, acc)) return rc;
     qk_conv_desc_t lin = *d;
     lin.activation = QK_ACT_LINEAR;
     return conv_bwd_data_impl(&lin, dym, nullptr, w, dx, ws, bd, stream, dx_mask);
 }
 
-qk_conv_desc_t dense_as_conv(const qk_dense_desc_t *d)
+// qk_dense_desc_t -> the validated descriptor of the rank-0 convolution that computes it
+int dense_as_conv(const qk_dense_desc_t *d, qk_conv_desc_t *cp)
 {
-    qk_conv_desc_t c;
+    if (!d) { set_error("descriptor is NULL"); return QK_ERR_INVALID_ARG; }
+    qk_conv_desc_t &c = *cp;
     memset(&c, 0, sizeof(c));
     c.rank = 0; c.batch = d->rows; c.cq = d->in_q; c.fq = d->q_units;
     for (int i = 0; i < 3; ++i) {
@@ -659,8 +653,11 @@ qk_conv_desc_t dense_as_conv(const qk_dense_desc_t *d)
     c.layout = QK_CH_LAST; c.dtype = d->dtype; c.activation = d->activation;
     c.has_bias = d->has_bias; c.conj = 1;     // dense.py:139-143 is the transposed table
     c.ws_has_kernel = d->ws_has_kernel;
-    return c;
+    return validate(&c, true);
 }
+
+// qk_*_bwd_weight[_acc]: the workspace doubles as the masked-dy side output when it can hold one
+void *masked_dy_slot(const qk_conv_desc_t *d, void *ws, size_t wsb) { return (ws && wsb >= dy_bytes(d) && aligned(ws, 16)) ? ws : nullptr; }
 
 int check_launch(int rc, const char *what)
 {
@@ -725,9 +722,8 @@ size_t qk_conv_workspace_bytes(const qk_conv_desc_t *desc, int op)
 
 size_t qk_dense_workspace_bytes(const qk_dense_desc_t *desc, int op)
 {
-    if (!desc) return 0;
-    const qk_conv_desc_t c = dense_as_conv(desc);
-    if (validate(&c, true)) return 0;
+    qk_conv_desc_t c;
+    if (dense_as_conv(desc, &c)) return 0;
     return ws_bytes_impl(&c, op);
 }
 
@@ -803,8 +799,7 @@ int qk_conv_bwd_weight(const qk_conv_desc_t *desc, const void *x, const void *dy
                        float *dbias, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (int rc = validate(desc, false)) return rc;
-    void *dym = (workspace && workspace_bytes >= dy_bytes(desc) && aligned(workspace, 16)) ? workspace : nullptr;
-    return check_launch(conv_bwd_weight_impl(desc, x, dy, y, dw, dbias, dym, (hipStream_t)stream, false, workspace, workspace_bytes), "qk_conv_bwd_weight");
+    return check_launch(conv_bwd_weight_impl(desc, x, dy, y, dw, dbias, masked_dy_slot(desc, workspace, workspace_bytes), (hipStream_t)stream, false, workspace, workspace_bytes), "qk_conv_bwd_weight");
 }
 
 int qk_conv_bwd_chain(const qk_conv_desc_t *desc, const void *x, const void *dy, const void *y, const float *w,
@@ -820,9 +815,8 @@ int qk_dense_bwd_chain(const qk_dense_desc_t *desc, const void *x, const void *d
                        void *dx, float *dw, float *dbias, int32_t flags, void *workspace, size_t workspace_bytes,
                        void *stream)
 {
-    if (!desc) { set_error("descriptor is NULL"); return QK_ERR_INVALID_ARG; }
-    const qk_conv_desc_t c = dense_as_conv(desc);
-    if (int rc = validate(&c, true)) return rc;
+    qk_conv_desc_t c;
+    if (int rc = dense_as_conv(desc, &c)) return rc;
     if ((flags & QK_BWD_MASK_DX) && !x) { set_error("QK_BWD_MASK_DX needs x"); return QK_ERR_INVALID_ARG; }
     return check_launch(conv_bwd_impl(&c, x, dy, y, w, dx, dw, dbias, workspace, workspace_bytes, (hipStream_t)stream, flags), "qk_dense_bwd_chain");
 }
@@ -831,18 +825,15 @@ int qk_conv_bwd_weight_acc(const qk_conv_desc_t *desc, const void *x, const void
                            float *dw, float *dbias, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (int rc = validate(desc, false)) return rc;
-    void *dym = (workspace && workspace_bytes >= dy_bytes(desc) && aligned(workspace, 16)) ? workspace : nullptr;
-    return check_launch(conv_bwd_weight_impl(desc, x, dy, y, dw, dbias, dym, (hipStream_t)stream, true, workspace, workspace_bytes), "qk_conv_bwd_weight_acc");
+    return check_launch(conv_bwd_weight_impl(desc, x, dy, y, dw, dbias, masked_dy_slot(desc, workspace, workspace_bytes), (hipStream_t)stream, true, workspace, workspace_bytes), "qk_conv_bwd_weight_acc");
 }
 
 int qk_dense_bwd_weight_acc(const qk_dense_desc_t *desc, const void *x, const void *dy, const void *y,
                             float *dw, float *dbias, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!desc) { set_error("descriptor is NULL"); return QK_ERR_INVALID_ARG; }
-    const qk_conv_desc_t c = dense_as_conv(desc);
-    if (int rc = validate(&c, true)) return rc;
-    void *dym = (workspace && workspace_bytes >= dy_bytes(&c) && aligned(workspace, 16)) ? workspace : nullptr;
-    return check_launch(conv_bwd_weight_impl(&c, x, dy, y, dw, dbias, dym, (hipStream_t)stream, true), "qk_dense_bwd_weight_acc");
+    qk_conv_desc_t c;
+    if (int rc = dense_as_conv(desc, &c)) return rc;
+    return check_launch(conv_bwd_weight_impl(&c, x, dy, y, dw, dbias, masked_dy_slot(&c, workspace, workspace_bytes), (hipStream_t)stream, true), "qk_dense_bwd_weight_acc");
 }
 
 int qk_conv_bwd(const qk_conv_desc_t *desc, const void *x, const void *dy, const void *y, const float *w,
@@ -855,38 +846,33 @@ int qk_conv_bwd(const qk_conv_desc_t *desc, const void *x, const void *dy, const
 int qk_dense_bwd(const qk_dense_desc_t *desc, const void *x, const void *dy, const void *y, const float *w,
                  void *dx, float *dw, float *dbias, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!desc) { set_error("descriptor is NULL"); return QK_ERR_INVALID_ARG; }
-    const qk_conv_desc_t c = dense_as_conv(desc);
-    if (int rc = validate(&c, true)) return rc;
+    qk_conv_desc_t c;
+    if (int rc = dense_as_conv(desc, &c)) return rc;
     return check_launch(conv_bwd_impl(&c, x, dy, y, w, dx, dw, dbias, workspace, workspace_bytes, (hipStream_t)stream), "qk_dense_bwd");
 }
 
 int qk_dense_fwd(const qk_dense_desc_t *desc, const void *x, const float *w, const float *bias, void *y,
                  void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!desc) { set_error("descriptor is NULL"); return QK_ERR_INVALID_ARG; }
-    const qk_conv_desc_t c = dense_as_conv(desc);
-    if (int rc = validate(&c, true)) return rc;
+    qk_conv_desc_t c;
+    if (int rc = dense_as_conv(desc, &c)) return rc;
     return check_launch(conv_fwd_impl(&c, x, w, bias, y, workspace, workspace_bytes, (hipStream_t)stream), "qk_dense_fwd");
 }
 
 int qk_dense_bwd_data(const qk_dense_desc_t *desc, const void *dy, const void *y, const float *w, void *dx,
                       void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!desc) { set_error("descriptor is NULL"); return QK_ERR_INVALID_ARG; }
-    const qk_conv_desc_t c = dense_as_conv(desc);
-    if (int rc = validate(&c, true)) return rc;
+    qk_conv_desc_t c;
+    if (int rc = dense_as_conv(desc, &c)) return rc;
     return check_launch(conv_bwd_data_impl(&c, dy, y, w, dx, workspace, workspace_bytes, (hipStream_t)stream), "qk_dense_bwd_data");
 }
 
 int qk_dense_bwd_weight(const qk_dense_desc_t *desc, const void *x, const void *dy, const void *y, float *dw,
                         float *dbias, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!desc) { set_error("descriptor is NULL"); return QK_ERR_INVALID_ARG; }
-    const qk_conv_desc_t c = dense_as_conv(desc);
-    if (int rc = validate(&c, true)) return rc;
-    void *dym = (workspace && workspace_bytes >= dy_bytes(&c) && aligned(workspace, 16)) ? workspace : nullptr;
-    return check_launch(conv_bwd_weight_impl(&c, x, dy, y, dw, dbias, dym, (hipStream_t)stream), "qk_dense_bwd_weight");
+    qk_conv_desc_t c;
+    if (int rc = dense_as_conv(desc, &c)) return rc;
+    return check_launch(conv_bwd_weight_impl(&c, x, dy, y, dw, dbias, masked_dy_slot(&c, workspace, workspace_bytes), (hipStream_t)stream), "qk_dense_bwd_weight");
 }
 
 static bool conv1_pool_ok(const qk_conv_desc_t *d, int32_t pool, int act = QK_ACT_RELU)
@@ -908,41 +894,6 @@ size_t qk_conv_relu_pool_aux_bytes(const qk_conv_desc_t *desc, int32_t pool)
     return conv1_pool_argbits_bytes(desc->batch, desc->in_spatial[0], desc->in_spatial[1], desc->fq);
 }
 
-int qk_conv_relu_pool_fwd(const qk_conv_desc_t *desc, int32_t pool, const void *x, const float *w, const float *bias,
-                          void *pooled, void *aux, void *stream)
-{
-    if (int rc = validate(desc, false)) return rc;
-    if (!conv1_pool_ok(desc, pool)) { set_error("qk_conv_relu_pool: geometry outside the fused first-layer kernel (see include/qk.h)"); return QK_ERR_UNSUPPORTED; }
-    if (!x || !w || !pooled || (desc->has_bias && !bias)) { set_error("qk_conv_relu_pool_fwd: NULL argument"); return QK_ERR_INVALID_ARG; }
-    if (!aligned(x, 8) || !aligned(pooled, 16) || (aux && !aligned(aux, 16))) { set_error("qk_conv_relu_pool_fwd: alignment"); return QK_ERR_INVALID_ARG; }
-    note_path(QK_PATH_MFMA16);
-    ProfScope prof_scope(QK_OP_FWD, desc, (hipStream_t)stream);
-    return check_launch(launch_conv1_pool(desc->dtype, false, x, w, bias, pooled, aux, nullptr, nullptr, desc->batch, desc->in_spatial[0],
-                                          desc->in_spatial[1], desc->fq, desc->has_bias, (hipStream_t)stream, nullptr, 0, nullptr, nullptr,
-                                          desc->layout == QK_CH_FIRST), "qk_conv_relu_pool_fwd");
-}
-
-int qk_conv_relu_pool_bwd(const qk_conv_desc_t *desc, int32_t pool, const void *x, const void *dpooled, const void *aux,
-                          float *dw, float *dbias, int32_t flags, void *stream)
-{
-    if (int rc = validate(desc, false)) return rc;
-    if (flags & ~QK_BWD_ACCUMULATE) { set_error("qk_conv_relu_pool_bwd: only QK_BWD_ACCUMULATE is a valid flag (0x%x)", flags); return QK_ERR_INVALID_ARG; }
-    if (!conv1_pool_ok(desc, pool)) { set_error("qk_conv_relu_pool: geometry outside the fused first-layer kernel (see include/qk.h)"); return QK_ERR_UNSUPPORTED; }
-    if (!x || !dpooled || !aux || !dw || (desc->has_bias && !dbias)) { set_error("qk_conv_relu_pool_bwd: NULL argument"); return QK_ERR_INVALID_ARG; }
-    if (!aligned(x, 8) || !aligned(dpooled, 16) || !aligned(aux, 16)) { set_error("qk_conv_relu_pool_bwd: alignment"); return QK_ERR_INVALID_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    note_path(QK_PATH_MFMA16);
-    ProfScope prof_scope(QK_OP_BWD_WEIGHT, desc, st);
-    if (!(flags & QK_BWD_ACCUMULATE) &&
-        (hipMemsetAsync(dw, 0, w_floats(desc) * sizeof(float), st) != hipSuccess ||
-         (desc->has_bias && hipMemsetAsync(dbias, 0, 4 * (size_t)desc->fq * sizeof(float), st) != hipSuccess))) {
-        set_error("memset dw failed"); return QK_ERR_LAUNCH;
-    }
-    return check_launch(launch_conv1_pool(desc->dtype, true, x, nullptr, nullptr, dpooled, const_cast<void *>(aux), dw, desc->has_bias ? dbias : nullptr,
-                                          desc->batch, desc->in_spatial[0], desc->in_spatial[1], desc->fq, desc->has_bias, st, nullptr, 0, nullptr,
-                                          nullptr, desc->layout == QK_CH_FIRST), "qk_conv_relu_pool_bwd");
-}
-
 // PReLU form of the fused first layer: slopes per row of the conv output (alpha_axis 0, alpha_len == in_spatial[0] <= 64)
 // or one slope (alpha_axis -1); no dropout (the reference has none between the first convolution and its pooling)
 static int prelu_pool_post_ok(const qk_conv_desc_t *desc, const qk_postop_t *post)
@@ -955,30 +906,39 @@ static int prelu_pool_post_ok(const qk_conv_desc_t *desc, const qk_postop_t *pos
     return QK_OK;
 }
 
-int qk_conv_prelu_pool_fwd(const qk_conv_desc_t *desc, int32_t pool, const qk_postop_t *post, const void *x, const float *w,
-                           const float *bias, void *pooled, void *pre_pooled, void *aux, void *stream)
+// The relu and the PReLU form of the fused first layer share one body per direction.  fn: the entry point
+// (qk_conv_{relu,prelu}_pool_{fwd,bwd}; its name without the direction heads the messages about the layer itself);
+// prelu: the convolution is LINEAR and `post` holds the slopes.  conv1_pool_checks: what both directions check first.
+static int conv1_pool_checks(const char *fn, const qk_conv_desc_t *desc, int32_t pool, bool prelu, const qk_postop_t *post, int32_t flags)
 {
     if (int rc = validate(desc, false)) return rc;
-    if (!conv1_pool_ok(desc, pool, QK_ACT_LINEAR)) { set_error("qk_conv_prelu_pool: geometry outside the fused first-layer kernel (see include/qk.h)"); return QK_ERR_UNSUPPORTED; }
-    if (int rc = prelu_pool_post_ok(desc, post)) return rc;
-    if (!x || !w || !pooled || (desc->has_bias && !bias)) { set_error("qk_conv_prelu_pool_fwd: NULL argument"); return QK_ERR_INVALID_ARG; }
-    if (!aligned(x, 8) || !aligned(pooled, 16) || (aux && !aligned(aux, 16)) || (pre_pooled && !aligned(pre_pooled, 16))) { set_error("qk_conv_prelu_pool_fwd: alignment"); return QK_ERR_INVALID_ARG; }
+    if (flags & ~QK_BWD_ACCUMULATE) { set_error("%s: only QK_BWD_ACCUMULATE is a valid flag (0x%x)", fn, flags); return QK_ERR_INVALID_ARG; }
+    if (!conv1_pool_ok(desc, pool, prelu ? QK_ACT_LINEAR : QK_ACT_RELU)) {
+        set_error("%.*s: geometry outside the fused first-layer kernel (see include/qk.h)", (int)strlen(fn) - 4, fn); return QK_ERR_UNSUPPORTED;
+    }
+    return prelu ? prelu_pool_post_ok(desc, post) : QK_OK;
+}
+
+static int conv1_pool_fwd(const char *fn, const qk_conv_desc_t *desc, int32_t pool, bool prelu, const qk_postop_t *post, const void *x,
+                          const float *w, const float *bias, void *pooled, void *pre_pooled, void *aux, void *stream)
+{
+    if (int rc = conv1_pool_checks(fn, desc, pool, prelu, post, 0)) return rc;
+    if (!x || !w || !pooled || (desc->has_bias && !bias)) { set_error("%s: NULL argument", fn); return QK_ERR_INVALID_ARG; }
+    if (!aligned(x, 8) || !aligned(pooled, 16) || (aux && !aligned(aux, 16)) || (pre_pooled && !aligned(pre_pooled, 16))) { set_error("%s: alignment", fn); return QK_ERR_INVALID_ARG; }
     note_path(QK_PATH_MFMA16);
     ProfScope prof_scope(QK_OP_FWD, desc, (hipStream_t)stream);
     return check_launch(launch_conv1_pool(desc->dtype, false, x, w, bias, pooled, aux, nullptr, nullptr, desc->batch, desc->in_spatial[0],
-                                          desc->in_spatial[1], desc->fq, desc->has_bias, (hipStream_t)stream, post->alpha, post->alpha_len,
-                                          pre_pooled, nullptr, desc->layout == QK_CH_FIRST), "qk_conv_prelu_pool_fwd");
+                                          desc->in_spatial[1], desc->fq, desc->has_bias, (hipStream_t)stream, prelu ? post->alpha : nullptr,
+                                          prelu ? post->alpha_len : 0, pre_pooled, nullptr, desc->layout == QK_CH_FIRST), fn);
 }
 
-int qk_conv_prelu_pool_bwd(const qk_conv_desc_t *desc, int32_t pool, const qk_postop_t *post, const void *x, const void *dpooled,
-                           const void *pre_pooled, const void *aux, float *dw, float *dbias, float *dalpha, int32_t flags, void *stream)
+static int conv1_pool_bwd(const char *fn, const qk_conv_desc_t *desc, int32_t pool, bool prelu, const qk_postop_t *post, const void *x,
+                          const void *dpooled, const void *pre_pooled, const void *aux, float *dw, float *dbias, float *dalpha, int32_t flags,
+                          void *stream)
 {
-    if (int rc = validate(desc, false)) return rc;
-    if (flags & ~QK_BWD_ACCUMULATE) { set_error("qk_conv_prelu_pool_bwd: only QK_BWD_ACCUMULATE is a valid flag (0x%x)", flags); return QK_ERR_INVALID_ARG; }
-    if (!conv1_pool_ok(desc, pool, QK_ACT_LINEAR)) { set_error("qk_conv_prelu_pool: geometry outside the fused first-layer kernel (see include/qk.h)"); return QK_ERR_UNSUPPORTED; }
-    if (int rc = prelu_pool_post_ok(desc, post)) return rc;
-    if (!x || !dpooled || !pre_pooled || !aux || !dw || (desc->has_bias && !dbias)) { set_error("qk_conv_prelu_pool_bwd: NULL argument"); return QK_ERR_INVALID_ARG; }
-    if (!aligned(x, 8) || !aligned(dpooled, 16) || !aligned(pre_pooled, 16) || !aligned(aux, 16)) { set_error("qk_conv_prelu_pool_bwd: alignment"); return QK_ERR_INVALID_ARG; }
+    if (int rc = conv1_pool_checks(fn, desc, pool, prelu, post, flags)) return rc;
+    if (!x || !dpooled || (prelu && !pre_pooled) || !aux || !dw || (desc->has_bias && !dbias)) { set_error("%s: NULL argument", fn); return QK_ERR_INVALID_ARG; }
+    if (!aligned(x, 8) || !aligned(dpooled, 16) || !aligned(pre_pooled, 16) || !aligned(aux, 16)) { set_error("%s: alignment", fn); return QK_ERR_INVALID_ARG; }
     hipStream_t st = (hipStream_t)stream;
     note_path(QK_PATH_MFMA16);
     ProfScope prof_scope(QK_OP_BWD_WEIGHT, desc, st);
@@ -988,8 +948,33 @@ int qk_conv_prelu_pool_bwd(const qk_conv_desc_t *desc, int32_t pool, const qk_po
         set_error("memset dw failed"); return QK_ERR_LAUNCH;
     }
     return check_launch(launch_conv1_pool(desc->dtype, true, x, nullptr, nullptr, dpooled, const_cast<void *>(aux), dw, desc->has_bias ? dbias : nullptr,
-                                          desc->batch, desc->in_spatial[0], desc->in_spatial[1], desc->fq, desc->has_bias, st, post->alpha,
-                                          post->alpha_len, pre_pooled, dalpha, desc->layout == QK_CH_FIRST), "qk_conv_prelu_pool_bwd");
+                                          desc->batch, desc->in_spatial[0], desc->in_spatial[1], desc->fq, desc->has_bias, st,
+                                          prelu ? post->alpha : nullptr, prelu ? post->alpha_len : 0, pre_pooled, dalpha,
+                                          desc->layout == QK_CH_FIRST), fn);
+}
+
+int qk_conv_relu_pool_fwd(const qk_conv_desc_t *desc, int32_t pool, const void *x, const float *w, const float *bias,
+                          void *pooled, void *aux, void *stream)
+{
+    return conv1_pool_fwd("qk_conv_relu_pool_fwd", desc, pool, false, nullptr, x, w, bias, pooled, nullptr, aux, stream);
+}
+
+int qk_conv_relu_pool_bwd(const qk_conv_desc_t *desc, int32_t pool, const void *x, const void *dpooled, const void *aux,
+                          float *dw, float *dbias, int32_t flags, void *stream)
+{
+    return conv1_pool_bwd("qk_conv_relu_pool_bwd", desc, pool, false, nullptr, x, dpooled, nullptr, aux, dw, dbias, nullptr, flags, stream);
+}
+
+int qk_conv_prelu_pool_fwd(const qk_conv_desc_t *desc, int32_t pool, const qk_postop_t *post, const void *x, const float *w,
+                           const float *bias, void *pooled, void *pre_pooled, void *aux, void *stream)
+{
+    return conv1_pool_fwd("qk_conv_prelu_pool_fwd", desc, pool, true, post, x, w, bias, pooled, pre_pooled, aux, stream);
+}
+
+int qk_conv_prelu_pool_bwd(const qk_conv_desc_t *desc, int32_t pool, const qk_postop_t *post, const void *x, const void *dpooled,
+                           const void *pre_pooled, const void *aux, float *dw, float *dbias, float *dalpha, int32_t flags, void *stream)
+{
+    return conv1_pool_bwd("qk_conv_prelu_pool_bwd", desc, pool, true, post, x, dpooled, pre_pooled, aux, dw, dbias, dalpha, flags, stream);
 }
 
 int qk_conv_fold_taps(const qk_conv_desc_t *desc, const void *x, void *xcol, int32_t cq2, void *stream)
@@ -1000,18 +985,7 @@ int qk_conv_fold_taps(const qk_conv_desc_t *desc, const void *x, void *xcol, int
         set_error("cq2 = %d must be a multiple of 8 and >= taps*cq = %d", cq2, taps_of(desc) * desc->cq);
         return QK_ERR_INVALID_ARG;
     }
-    GemmGeom g;
-    memset(&g, 0, sizeof(g));
-    const Strides xs = act_strides(desc->in_spatial, 4 * desc->cq, desc->layout);
-    g.batch = desc->batch;
-    g.M = desc->batch * desc->out_spatial[0] * desc->out_spatial[1] * desc->out_spatial[2];
-    g.Q = desc->cq; g.taps = taps_of(desc);
-    for (int i = 0; i < 3; ++i) {
-        g.osp[i] = desc->out_spatial[i]; g.isp[i] = desc->in_spatial[i]; g.ks[i] = desc->kernel[i];
-        g.pa[i] = desc->stride[i]; g.pb[i] = desc->dilation[i]; g.pc[i] = -desc->pad_lo[i]; g.pd[i] = 1;
-        g.in_ss[i] = xs.ss[i];
-    }
-    g.in_sn = xs.sn; g.in_sc = xs.sc;
+    const GemmGeom g = make_geom(desc, false);            // (the gather side of the forward geometry is all k_fold_taps reads)
     if ((long long)g.M * 4 * cq2 > INT_MAX) { set_error("folded tensor has >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
     return check_launch(launch_fold_taps(desc->dtype, x, xcol, g, cq2, (hipStream_t)stream), "qk_conv_fold_taps");
 }
@@ -1417,17 +1391,14 @@ int qk_conv_prep_kernels(int32_t n, const qk_conv_desc_t *const *descs, const in
                 j.small = 0; j.kin = 0; j.n_ot = 0;
                 j.ch_major = d->kernel_order == QK_KERNEL_CHANNEL_MAJOR;
                 j.neg_ijk = bwd ? (d->conj ? 1 : 0) : (d->conj ? 0 : 1);       // the sign table go16 folds into the kernel
-                {   // 16 / 32-channel layers: a second job writes the fragment layout of k_hconv16_small into the region behind the band
-                    // layout (the shape alone decides that the region exists, exactly as go16 and qk_conv_workspace_bytes see it)
-                    GemmGeom sg, sbg;
-                    Small16 sm;
-                    prep_geom(d, bwd, &sg);
-                    if (d->layout == QK_CH_LAST && !j.ch_major && small16_shape(sg, &sbg, &sm)) {
-                        PrepJob &k = jobs.j[m++];
-                        k = j;
-                        k.wq = static_cast<char *>(workspaces[i]) + (size_t)j.taps * pad32(d->cq) * 4 * pad32(d->fq) * 2 + 256;
-                        k.small = 1; k.kin = sm.kin; k.n_ot = sm.n_ot;
-                    }
+                // 16 / 32-channel layers: a second job writes the fragment layout of k_hconv16_small into the region behind the band
+                // layout (the shape alone decides that the region exists, exactly as go16 and qk_conv_workspace_bytes see it)
+                const KernelWs kw = kernel_ws(d, bwd ? QK_OP_BWD_DATA : QK_OP_FWD);
+                if (kw.small) {
+                    PrepJob &k = jobs.j[m++];
+                    k = j;
+                    k.wq = static_cast<char *>(workspaces[i]) + kw.band;
+                    k.small = 1; k.kin = kw.sm.kin; k.n_ot = kw.sm.n_ot;
                 }
             }
             if (m >= 31 || (i == n && m > 0)) {

@@ -92,6 +92,11 @@ struct GemmGeom {
     int w_ch_major;     // qk_conv_desc_t.kernel_order == QK_KERNEL_CHANNEL_MAJOR: the compact kernel lies as (cq, taps, 4 fq); honoured by the 16-bit re-layout only
 };
 
+inline int pad32(int v) { return (v + 31) / 32 * 32; }
+// bytes of the band-layout 16-bit image of a compact kernel in a workspace: [taps][Qp][4][Jp] 16-bit values (Qp, Jp: the channel
+// counts rounded up to the kernels' 32-channel granule, GemmGeom::Qp / Jp) and a 256-byte zero line behind them
+inline size_t band_image_bytes(int taps, int Qp, int Jp) { return (size_t)taps * Qp * 4 * Jp * 2 + 256; }
+
 // Backward-weight geometry:  dW[t, c, p, f] = sum_{a^b=p} sgn(a,b) sum_m x_a[pos(m,t), c] * dy_b[m, f]
 // Geometry of the band variants of the forward / backward-data kernels (qk_hgemm_bf16mfma.hip,
 // qk_hgemm_f32mfma.inc), or false when the shape is outside them: the innermost used axis must have
@@ -126,8 +131,8 @@ inline bool band_geom(const GemmGeom &g, int esize, GemmGeom *o)
     const long long lines = (long long)g.batch * o->osp[0] * o->osp[1];
     if (lines * o->b_wp >= (1ll << 31) - 512) return false;
     o->b_nlines = (int)lines;
-    const long long Qw = g.Qp ? g.Qp : g.Q, Jw = g.Jp ? g.Jp : g.J;             // (padded extents of the re-laid-out kernel, 16-bit path)
-    const long long in_bytes = (long long)g.batch * g.in_sn * esize, w_bytes = (long long)g.taps * Qw * 4 * Jw * 2 + 256;
+    const int Qw = g.Qp ? g.Qp : g.Q, Jw = g.Jp ? g.Jp : g.J;                   // (padded extents of the re-laid-out kernel, 16-bit path)
+    const long long in_bytes = (long long)g.batch * g.in_sn * esize, w_bytes = (long long)band_image_bytes(g.taps, Qw, Jw);
     if (in_bytes >= 0xF0000000ll || w_bytes >= 0xF0000000ll) return false;   // 32-bit buffer offsets
     o->b_in_bytes = (unsigned)in_bytes;
     o->b_w_bytes = (unsigned)w_bytes;
@@ -137,7 +142,6 @@ inline bool band_geom(const GemmGeom &g, int esize, GemmGeom *o)
     return true;
 }
 
-inline int pad32(int v) { return (v + 31) / 32 * 32; }
 
 // n / d for 0 <= n < 2^31 with (mul, shr) from fastdiv_of(d): umulhi(n, mul) >> shr  (d == 1: mul == 0 marks identity)
 inline void fastdiv_of(unsigned d, unsigned *mul, unsigned *shr)

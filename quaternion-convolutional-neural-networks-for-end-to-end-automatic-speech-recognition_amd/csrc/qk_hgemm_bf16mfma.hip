@@ -1413,7 +1413,7 @@ int go16(const void *in, const void *mask, const float *w, const float *bias, vo
         // everything else the small kernel, in any order, on the same buffer.  A workspace without room for the second region
         // (a caller that sized it by hand for the band form) runs the band form.
         Small16 sm;
-        const size_t band_bytes = (size_t)g.taps * g.Qp * 4 * g.Jp * 2 + 256;
+        const size_t band_bytes = band_image_bytes(g.taps, g.Qp, g.Jp);
         if (!g.w_ch_major && small16_shape(g, &bg, &sm) && ws_bytes >= band_bytes + small16_region_bytes(sm)) {
             T *wqs = reinterpret_cast<T *>(static_cast<char *>(ws) + band_bytes);
             if (!g.w_prepped) {                       // a cache miss fills BOTH regions: the caller may flag the buffer as prepped from now on
@@ -1525,8 +1525,7 @@ int try_hgemm_16(int dtype, const void *in, const void *mask, const float *w_f32
     if (g.out_sn != S * g.out_ss) return 0;
     if (g.Q % 16 != 0 || g.J % 16 != 0) return 0;                      // (multiples of 16 but not 32: zero-padded band form, go16)
     if (g.taps > 32 || g.pd[0] != 1 || g.pd[1] != 1 || g.pd[2] != 1) return 0;   // tap bit mask; unit-stride map
-    const size_t need = (size_t)g.taps * pad32(g.Q) * 4 * pad32(g.J) * 2 + 256;
-    if (!ws || ws_bytes < need) return 0;
+    if (!ws || ws_bytes < band_image_bytes(g.taps, pad32(g.Q), pad32(g.J))) return 0;
     if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(mask)) & 15) return 0;
     if (debug_flags() & kDbgNoMfma16) return 0;                        // diagnostic switch
     if (dtype == QK_BF16) return go16<bf16>(in, mask, w_f32, bias, out, g, w_is_transposed, ws, ws_bytes, stream);

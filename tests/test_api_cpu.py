@@ -63,6 +63,94 @@ def test_invalid_descriptor_is_rejected_without_gpu():
     assert b'NULL' in lib.qk_last_error()
 
 
+def _workspace_cases():
+    """(id, call) for every descriptor of the workspace-size table: every combination the dispatcher's size and layout code
+    branches on -- dtype, (cq, fq), tap count, activation, layout, stride, kernel_order, rank, dense."""
+    bf, hf, f32 = torch.bfloat16, torch.float16, torch.float32
+    cases = []
+
+    def conv(name, rank, sp, ks, cq, fq, dtype, act, layout='channels_last', batch=2, **kw):
+        xs = (batch, 4 * cq) + tuple(sp) if layout == 'channels_first' else (batch,) + tuple(sp) + (4 * cq,)
+        call = functional.conv_call(xs, tuple(ks) + (cq, 4 * fq), dtype, rank, layout=layout, activation=act, **kw)
+        cases.append(('%s_%s_%dto%d_%s' % (name, str(dtype)[6:], cq, fq, act or 'linear'), call))
+
+    def dense(rows, in_q, units_q, dtype, act):
+        call = functional.dense_call((rows, 4 * in_q), (in_q, 4 * units_q), dtype, act, True)
+        cases.append(('dense_%s_%dto%d_%s' % (str(dtype)[6:], in_q, units_q, act or 'linear'), call))
+
+    # fp32: the kernels read the compact kernel in place -- only the fused backward's masked dy needs room
+    conv('c1d_3tap', 1, (50,), (3,), 40, 64, f32, 'relu', padding='same')
+    conv('c2d_3x5', 2, (6, 50), (3, 5), 32, 32, f32, None, padding='same')
+    conv('c2d_3x5_cf', 2, (6, 50), (3, 5), 32, 32, f32, 'relu', layout='channels_first', padding='same')
+    conv('c3d_2x3x3', 3, (4, 5, 20), (2, 3, 3), 4, 8, f32, 'relu', padding='same')
+    dense(33, 64, 32, f32, 'relu')
+    dense(33, 64, 32, f32, None)
+    pairs = [(8, 8), (8, 16), (16, 8), (16, 16), (16, 32), (32, 16), (48, 16), (16, 48), (32, 32), (32, 64), (64, 32), (48, 48),
+             (64, 64)]
+    for cq, fq in pairs:
+        conv('c2d_3x5', 2, (6, 50), (3, 5), cq, fq, bf, 'relu', padding='same')
+        conv('c2d_3x5', 2, (6, 50), (3, 5), cq, fq, hf, None, padding='same')
+        conv('c1d_1tap', 1, (50,), (1,), cq, fq, bf, None, batch=3, padding='same')
+    for cq, fq in [(8, 16), (16, 16), (16, 32), (48, 16), (32, 32), (32, 64)]:
+        conv('c2d_7x5_35taps', 2, (9, 50), (7, 5), cq, fq, hf, 'relu', padding='same')
+    # shapes at the edges of the small-channel and band kernels: stride 2, more than three outer taps, a dilated inner axis, lines
+    # too short for the band form, a 'valid' three-tap 1-D layer, conj
+    for cq, fq in [(16, 16), (32, 16), (32, 32), (32, 64)]:
+        conv('c1d_3tap_stride2', 1, (51,), (3,), cq, fq, bf, 'relu', padding='same', strides=2)
+        conv('c1d_3tap_valid', 1, (51,), (3,), cq, fq, hf, None, padding='valid')
+    for cq, fq in [(16, 16), (32, 16)]:
+        conv('c2d_5x5', 2, (8, 50), (5, 5), cq, fq, bf, None, padding='same')
+        conv('c2d_3x3_dil2', 2, (8, 50), (3, 3), cq, fq, bf, None, padding='same', dilation_rate=(1, 2))
+        conv('c2d_3x5_short_lines', 2, (8, 10), (3, 5), cq, fq, hf, 'relu', padding='same')
+        conv('c2d_3x5_conj', 2, (6, 50), (3, 5), cq, fq, bf, 'relu', padding='same', conj=True)
+    for cq, fq in [(16, 16), (32, 32)]:
+        conv('c3d_2x3x3', 3, (4, 5, 40), (2, 3, 3), cq, fq, bf, 'relu', padding='same')
+        conv('c3d_2x3x3', 3, (4, 5, 40), (2, 3, 3), cq, fq, hf, None, padding='same')
+    conv('c3d_1x3x3', 3, (4, 5, 40), (1, 3, 3), 16, 16, bf, 'relu', padding='same')
+    conv('c3d_3x3x5_45taps', 3, (4, 5, 40), (3, 3, 5), 32, 32, bf, 'relu', padding='same')
+    # channels_first: multiples of 32 with unit stride and at most 32 taps are re-laid out in the workspace, the rest are not
+    for cq, fq in [(16, 16), (48, 16), (32, 32), (32, 64), (64, 32)]:
+        conv('c2d_3x5_cf', 2, (7, 23), (3, 5), cq, fq, bf, 'relu', layout='channels_first', padding='same')
+        conv('c2d_3x5_cf', 2, (7, 23), (3, 5), cq, fq, hf, None, layout='channels_first', padding='same')
+        conv('c2d_3x5_cf_stride2', 2, (7, 23), (3, 5), cq, fq, bf, 'relu', layout='channels_first', padding='same', strides=(1, 2))
+    conv('c1d_3tap_cf', 1, (45,), (3,), 32, 32, bf, 'relu', layout='channels_first', batch=3, padding='valid')
+    conv('c1d_3tap_cf_stride2', 1, (45,), (3,), 32, 64, hf, None, layout='channels_first', batch=3, padding='same', strides=2)
+    conv('c3d_2x3x3_cf', 3, (4, 5, 21), (2, 3, 3), 32, 32, hf, 'relu', layout='channels_first', padding='same')
+    conv('c2d_7x5_35taps_cf', 2, (9, 23), (7, 5), 32, 32, bf, 'relu', layout='channels_first', padding='same')
+    # a dense weight read in place as the channel-major kernel of an (F, 1) 'valid' convolution
+    for cq, fq, dtype, act in [(32, 32, bf, 'relu'), (32, 64, hf, None), (64, 32, bf, None), (64, 64, hf, 'relu')]:
+        conv('c2d_6x1_ch_major', 2, (6, 50), (6, 1), cq, fq, dtype, act, batch=3, padding='valid', conj=True,
+             kernel_order=_lib.QK_KERNEL_CHANNEL_MAJOR)
+    for in_q, units_q in [(8, 8), (16, 16), (16, 32), (48, 16), (32, 64), (64, 64), (250, 128)]:
+        dense(77, in_q, units_q, bf, 'relu')
+        dense(77, in_q, units_q, hf, None)
+    assert len({c[0] for c in cases}) == len(cases)
+    return cases
+
+
+def _workspace_bytes(call):
+    fn = getattr(_lib.lib(), call.ws_fn)
+    return [int(fn(ctypes.byref(call.desc), op)) for op in (_lib.QK_OP_FWD, _lib.QK_OP_BWD_DATA, _lib.QK_OP_BWD_WEIGHT, _lib.QK_OP_BWD)]
+
+
+def test_workspace_sizes_are_those_of_the_hand_written_dispatcher():
+    """qk_conv_workspace_bytes / qk_dense_workspace_bytes of all four operations over the table of _workspace_cases(), against
+    tests/golden/g18_dispatcher.json ('workspace_bytes': id -> [fwd, bwd_data, bwd_weight, bwd]).  The values were recorded once,
+    with {id: _workspace_bytes(call)} over the same table, from a build of the commit BEFORE the dispatcher got one geometry
+    builder and one workspace-layout source: callers size, cache and refresh their workspaces by these figures, so the refactored
+    size code must reproduce every one of them."""
+    with open(os.path.join(GOLDEN, 'g18_dispatcher.json')) as f:
+        want = json.load(f)['workspace_bytes']
+    cases = _workspace_cases()
+    assert sorted(want) == sorted(c[0] for c in cases)
+    assert 60 <= len(cases)
+    got = {name: _workspace_bytes(call) for name, call in cases}
+    wrong = {name: (got[name], want[name]) for name in got if got[name] != want[name]}
+    assert not wrong, wrong
+    fp32 = [v for name, v in got.items() if '_float32_' in name]
+    assert fp32 and all(v[:3] == [0, 0, 0] for v in fp32)
+
+
 def test_cpu_tensors_raise_instead_of_falling_back():
     with pytest.raises(RuntimeError, match='no CPU fallback'):
         QuaternionConv1D(2, 3)(torch.randn(1, 5, 8))

@@ -923,6 +923,65 @@ def test_half_native_channels_first_layout_matches_oracle(case, dtype):
         assert err <= (tol16 if k in ('y', 'dx') else tol32), '%s: rel err %.3g' % (k, err)
 
 
+def _dispatch_cases():
+    """(id, rank, x_shape, w_shape, kwargs, native): HALF_CASES and RAGGED_CASES on physically channels_last buffers, NATIVE_16BIT
+    on true channels_first ones."""
+    out = []
+    for group, cases, native in (('half', HALF_CASES, False), ('ragged', RAGGED_CASES, False), ('native', NATIVE_16BIT, True)):
+        out += [('%s/%s' % (group, c[0]),) + tuple(c[1:]) + (native,) for c in cases]
+    return out
+
+
+def _dispatch_paths(case):
+    """qk_last_path() behind the forward, the backward-data and the backward-weight call of one case, in bf16."""
+    import qcnn_amd
+    from qcnn_amd import _lib
+    F = qcnn_amd.functional
+    dev = _dev()
+    _, rank, xs, ws, kw, native = case
+    dtype = torch.bfloat16
+    if rank == 0:
+        call = F.dense_call(tuple(xs), tuple(ws), dtype, kw.get('activation'), True)
+    else:
+        layout = kw.get('data_format', 'channels_last')
+        if layout == 'channels_first' and not native:
+            xs, layout = (xs[0],) + tuple(xs[2:]) + (xs[1],), 'channels_last'
+        call = F.conv_call(tuple(xs), tuple(ws), dtype, rank, kw.get('strides', 1), kw.get('padding', 'valid'), layout,
+                           kw.get('dilation_rate', 1), kw.get('activation'), True, kw.get('conj', False))
+    g = torch.Generator(device=dev).manual_seed(23)
+    x = torch.randn(xs, device=dev, generator=g).to(dtype)
+    w = torch.randn(ws, device=dev, generator=g) / 20
+    b = torch.randn(ws[-1], device=dev, generator=g) / 10
+    paths = []
+    y = call.fwd(x, w, b)
+    paths.append(_lib.last_path())
+    dy = torch.randn(y.shape, device=dev, generator=g).to(dtype)
+    call.bwd_data(dy, y if call.relu else None, w)
+    paths.append(_lib.last_path())
+    call.bwd_weight(x, dy, y if call.relu else None, True)
+    paths.append(_lib.last_path())
+    torch.cuda.synchronize()
+    return paths
+
+
+def test_every_small_case_is_served_by_the_kernel_family_recorded_for_it():
+    """A parity test still passes when a shape silently drops to a slower kernel family, so the dispatch itself is pinned:
+    qk_last_path() behind call.fwd, call.bwd_data and call.bwd_weight of every HALF_CASES, RAGGED_CASES and NATIVE_16BIT case in
+    bf16 -- the smallest shapes that reach the band, point, small-channel and general 16-bit kernels and the fp32-MFMA fallback --
+    against tests/golden/g18_dispatcher.json ('dispatch_paths': id -> [fwd, bwd_data, bwd_weight]), recorded with _dispatch_paths
+    on an MI355X from the build of the commit before the dispatcher's geometry and workspace layout got one source each."""
+    import json
+    from conftest import GOLDEN
+    with open(os.path.join(GOLDEN, 'g18_dispatcher.json')) as f:
+        want = json.load(f)['dispatch_paths']
+    cases = _dispatch_cases()
+    assert sorted(want) == sorted(c[0] for c in cases)
+    got = {c[0]: _dispatch_paths(c) for c in cases}
+    wrong = {k: (got[k], want[k]) for k in got if got[k] != want[k]}
+    assert not wrong, wrong
+    assert {p for v in got.values() for p in v} >= {'mfma16_band', 'mfma16_point', 'mfma16_small', 'mfma16', 'fp32_mfma'}
+
+
 @pytest.mark.parametrize('form', ['relu_dropout', 'prelu_dropout'])
 def test_channels_first_descriptor_with_post_ops_equals_channels_last(form):
     """QK_CH_FIRST at the C-ABI with a post-op (round 2: QK_ERR_UNSUPPORTED): qk_conv_fwd_post / qk_conv_bwd_post on true
