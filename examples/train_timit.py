@@ -29,6 +29,10 @@ together, as `sox speed` does) and multiplies it by a gain drawn from --volume L
 filter bank (qcnn_amd.features.SpeedPerturb, one launch, seeded from --seed).  The labels are unchanged: a sped-up utterance has
 fewer frames for the same labels.  Evaluation batches are never perturbed; it combines with --specaug.  No phone error rate has been
 measured with it.
+
+--align-eval adds to every evaluation the forced alignment of the held-out batch to its transcripts (TimitQCNN.align) and prints the
+share of phone boundaries it places within 20 ms of the hand-labelled ones in the .PHN files (a boundary is the centre of the
+phone's first frame, qcnn_amd.features.frames_to_samples).  Nobody has measured this figure for a trained model yet.
 """
 import argparse
 import fractions
@@ -41,16 +45,17 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
 import qcnn_amd  # noqa: E402,F401
-from qcnn_amd import dp, functional as F  # noqa: E402
-from qcnn_amd.data import TIMIT_PHONES_61, read_audio, read_phn, timit_61_to_39_class_map  # noqa: E402
-from qcnn_amd.features import SpecAugment, SpeedPerturb, quaternion_fbank  # noqa: E402
+from qcnn_amd import dp, functional as F, layers  # noqa: E402
+from qcnn_amd.data import TIMIT_PHONES_61, read_audio, read_phn, read_phn_segments, timit_61_to_39_class_map  # noqa: E402
+from qcnn_amd.features import SpecAugment, SpeedPerturb, frames_to_samples, quaternion_fbank  # noqa: E402
 from qcnn_amd.lm import NgramLM  # noqa: E402
 from qcnn_amd.models import getTimitModel2D  # noqa: E402
 from qcnn_amd.training import GradGuard  # noqa: E402
 
 
-def load_split(root):
-    """[(int16 samples, int32 phone classes)] of every WAV / PHN pair under root, sorted by path."""
+def load_split(root, boundaries=False):
+    """[(int16 samples, int32 phone classes)] of every WAV / PHN pair under root, sorted by path; with `boundaries` each entry also
+    carries the phones' hand-labelled start samples (int64)."""
     index = {p: c for c, p in enumerate(TIMIT_PHONES_61)}
     utts = []
     for d, _, files in sorted(os.walk(root)):
@@ -60,8 +65,12 @@ def load_split(root):
             if ext.lower() != '.wav' or (stem + '.phn').lower() not in by_lower:
                 continue
             wav = read_audio(os.path.join(d, f))
-            phones = read_phn(os.path.join(d, by_lower[(stem + '.phn').lower()]))
-            utts.append((wav, np.array([index[p] for p in phones], dtype=np.int32)))
+            phn = os.path.join(d, by_lower[(stem + '.phn').lower()])
+            phones = read_phn(phn)
+            utt = (wav, np.array([index[p] for p in phones], dtype=np.int32))
+            if boundaries:
+                utt += (np.array([seg[0] for seg in read_phn_segments(phn)], dtype=np.int64),)
+            utts.append(utt)
     return utts
 
 
@@ -111,6 +120,14 @@ def to_device(utts, idx, dev, dtype, augment=None, wave_augment=None):
     return x, frame_lengths[:, None], labels, label_length
 
 
+def reference_starts(utts, idx, width, dev):
+    """(B, width) int64 start samples of the batch's phones (load_split(boundaries=True)), padded with -1."""
+    ref = np.full((len(idx), width), -1, dtype=np.int64)
+    for r, i in enumerate(idx):
+        ref[r, :len(utts[i][2])] = utts[i][2]
+    return torch.from_numpy(ref).to(dev)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--timit', required=True, help='corpus root holding TRAIN/ and TEST/')
@@ -145,13 +162,15 @@ def main():
     ap.add_argument('--speeds', type=parse_speeds, default=((9, 10), (1, 1), (11, 10)),
                     help='speed perturbation: comma-separated speeds, each taken as a fraction with a denominator <= 32')
     ap.add_argument('--volume', type=parse_volume, default=(1.0, 1.0), help='speed perturbation: LO,HI of the linear gain drawn per utterance')
+    ap.add_argument('--align-eval', action='store_true',
+                    help='at every evaluation, force-align the held-out batch and print the share of boundaries within 20 ms of the .PHN ones')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
     dtype = getattr(torch, args.dtype)
 
     train = load_split(find_split(args.timit, 'TRAIN'))
-    test = load_split(find_split(args.timit, 'TEST'))
+    test = load_split(find_split(args.timit, 'TEST'), boundaries=args.align_eval)
     if not train:
         raise SystemExit('%s: no WAV / PHN pairs under TRAIN/' % args.timit)
     print('%d training and %d held-out utterances' % (len(train), len(test)))
@@ -213,6 +232,11 @@ def main():
             res = model.evaluate(xe, le, ile, lle, class_map=class_map)
             print('step %5d  held-out ctc cost %.4f  PER(39) %.4f (%d / %d)'
                   % (step, float(res.loss), float(res.per), int(res.errors), int(res.symbols)))
+            if args.align_eval:
+                ali = model.align(xe, le, ile, lle)
+                hits, total, share = layers.boundary_agreement(frames_to_samples(ali.starts), reference_starts(test, held_out, le.shape[1], dev),
+                                                               lle, tolerance=int(round(0.02 * 16000)))
+                print('step %5d  held-out boundary agreement within 20 ms %.4f (%d / %d)' % (step, float(share), int(hits), int(total)))
             if lm is not None:
                 plain = model.evaluate(xe, le, ile, lle, greedy=False, beam_width=args.beam_width, class_map=class_map)
                 fused = model.evaluate(xe, le, ile, lle, greedy=False, beam_width=args.beam_width, class_map=class_map, lm=lm,

@@ -471,6 +471,38 @@ int qk_ctc_beam_search_decode_lm(int32_t dtype, int32_t batch, int32_t frames, i
 int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
                      const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *distance, int32_t *ref_len_out, void *stream);
 
+/* ---- CTC forced alignment ----------------------------------------------------------------------------------------------------
+ * The best path of the CTC lattice of a KNOWN transcript: which frames belong to which label.  Inputs are those of
+ * qk_ctc_batch_cost: y_pred (batch, frames, classes) softmax outputs in `dtype` (fp32, bf16 or fp16), blank = classes - 1; labels
+ * (batch, max_label_len) int32; input_length, label_length (batch) int32.  Tn = min(max(input_length[b], 0), frames) and
+ * Ln = min(max(label_length[b], 0), max_label_len); labels outside [0, classes - 2] are clamped as the cost clamps them.
+ * max_label_len == 0 is allowed (labels, starts and ends may then be NULL).
+ *
+ * Emissions are exactly those of the cost: u[t][c] = log(y_pred[t][c] + 1e-7), lp[t][c] = u[t][c] - logsumexp_c u[t][.]; all
+ * arithmetic is fp32, 16-bit inputs are widened exactly.  States are the extended sequence l' = blank, l1, blank, ..., lL, blank
+ * (S = 2 Ln + 1); the transitions are those of the alpha recursion: stay, from s - 1, and from s - 2 when s is a label state and
+ * l'[s] != l'[s - 2].  A path starts in state 0 or 1 and ends in state S - 1 or S - 2.  The result is the path pi through the
+ * states that maximises sum_{t < Tn} lp[t][l'[pi_t]].
+ * Tie rule (the result is bit-repeatable): among equal predecessors stay wins over s - 1, and s - 1 over s - 2; at the end S - 1
+ * wins over S - 2; -inf never wins.
+ *
+ * Every element of every output is written by every call:
+ *   path   (batch, frames) int32         the class at each frame t < Tn (blank = classes - 1); -1 from Tn on;
+ *   starts, ends (batch, max_label_len) int32   the first frame of label i and one past its last frame -- the frames spent in
+ *                                        state 2 i + 1, contiguous by construction; both -1 for i >= Ln;
+ *   score  (batch) float32               the path's log-probability under lp, so that score <= -cost.
+ * An infeasible sample (more labels, counting a blank between repeats, than frames) gets score = -inf and path, starts, ends all
+ * -1.  Tn == 0: score = 0 if Ln == 0, else the infeasible result (path is all -1 either way).
+ *
+ * One workgroup per sample, one max-plus sweep with 2-bit back-pointers (64 bytes per frame), kept in LDS when the sample's frames
+ * fit and in the workspace otherwise, then a backtrack; the score is summed in a fixed order, without atomics.  Limits: classes <=
+ * 256, max_label_len <= 127, frames up to ~30 000 (LDS): QK_ERR_UNSUPPORTED beyond, as for an unknown dtype.  Workspace:
+ * qk_ctc_align_workspace_bytes (64 bytes per sample and frame), 8-byte aligned.  Launches on `stream` and never synchronises. */
+size_t qk_ctc_align_workspace_bytes(int32_t batch, int32_t frames, int32_t max_label_len);
+int qk_ctc_forced_align(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *labels,
+                        int32_t max_label_len, const int32_t *input_length, const int32_t *label_length, int32_t *path,
+                        int32_t *starts, int32_t *ends, float *score, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Acoustic front end ----------------------------------------------------------------------------------------------------
  * Waveforms -> the model's channels_first quaternion input out (batch, 4, F, frames), F = nfilt + (append_energy != 0): the
  * python_speech_features logfbank + delta recipe (the reference's Input(shape=(4, 41, None)), models/interspeech_model.py:81, with

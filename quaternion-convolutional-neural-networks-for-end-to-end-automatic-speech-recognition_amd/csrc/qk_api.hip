@@ -1137,6 +1137,39 @@ int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, cons
                                              distance, ref_len_out, (hipStream_t)stream), "qk_edit_distance");
 }
 
+size_t qk_ctc_align_workspace_bytes(int32_t batch, int32_t frames, int32_t max_label_len)
+{
+    if (batch <= 0 || frames <= 0 || max_label_len < 0) return 0;
+    return ctc_align_workspace_bytes(batch, frames);
+}
+
+int qk_ctc_forced_align(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *labels,
+                        int32_t max_label_len, const int32_t *input_length, const int32_t *label_length, int32_t *path,
+                        int32_t *starts, int32_t *ends, float *score, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (batch <= 0 || frames <= 0 || classes < 2 || max_label_len < 0) {
+        set_error("ctc_forced_align: bad extents (%d, %d, %d, %d)", batch, frames, classes, max_label_len); return QK_ERR_INVALID_ARG;
+    }
+    if (classes > 256 || max_label_len > 127 || dtype < QK_F32 || dtype > QK_F16) {
+        set_error("ctc_forced_align: unsupported (classes %d <= 256, max_label_len %d <= 127, dtype %d one of fp32 / bf16 / fp16)", classes,
+                  max_label_len, dtype);
+        return QK_ERR_UNSUPPORTED;
+    }
+    if (!y_pred || !input_length || !label_length || !path || !score || (max_label_len > 0 && (!labels || !starts || !ends))) {
+        set_error("ctc_forced_align: NULL argument"); return QK_ERR_INVALID_ARG;
+    }
+    if ((long long)batch * frames * classes > INT_MAX) { set_error("ctc_forced_align: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
+    if (!ctc_align_supported(frames, classes, max_label_len)) {
+        set_error("ctc_forced_align: %d frames are too many for one workgroup's LDS", frames); return QK_ERR_UNSUPPORTED;
+    }
+    const size_t need = ctc_align_workspace_bytes(batch, frames);
+    if (!workspace || workspace_bytes < need || !aligned(workspace, 8)) {
+        set_error("ctc_forced_align needs %zu workspace bytes (8-byte aligned), got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE;
+    }
+    return check_launch(launch_ctc_align(dtype, batch, frames, classes, y_pred, labels, max_label_len, input_length, label_length, path,
+                                         starts, ends, score, workspace, (hipStream_t)stream), "qk_ctc_forced_align");
+}
+
 int32_t qk_fbank_num_frames(int64_t samples, int32_t frame_len, int32_t frame_step)
 {
     if (frame_len < 1 || frame_step < 1) return 0;

@@ -357,6 +357,11 @@ int launch_ctc_beam_lm(int dtype, int B, int T, int C, const void *pred, const i
                        hipStream_t stream);
 int launch_edit_distance(int B, const int *hyp, int hs, const int *hl, const int *ref, int rs, const int *rl, const int *cmap,
                          int classes, int *out, int *rlen_out, hipStream_t stream);
+// CTC forced alignment (qk_ctc_align.hip)
+size_t ctc_align_workspace_bytes(int B, int T);
+bool ctc_align_supported(int T, int C, int Lmax);
+int launch_ctc_align(int dtype, int B, int T, int C, const void *pred, const int *labels, int Lmax, const int *in_len, const int *lab_len,
+                     int *path, int *starts, int *ends, float *score, void *ws, hipStream_t stream);
 // acoustic front end (qk_fbank.hip)
 struct FbankGeom {
     int B, n_max, T;            // utterances, samples per padded row, output frames

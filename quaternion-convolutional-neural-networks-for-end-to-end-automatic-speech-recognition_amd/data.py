@@ -61,6 +61,18 @@ def read_phn(path):
         return [line.split()[2] for line in f if line.strip()]
 
 
+def read_phn_segments(path):
+    """[(start_sample, end_sample, phone)] of a TIMIT .PHN file (lines `start end phone`), in order: the hand-labelled boundaries
+    read_phn leaves out -- the reference of a forced alignment (layers.boundary_agreement)."""
+    out = []
+    with open(path, 'r') as f:
+        for line in f:
+            if line.strip():
+                start, end, phone = line.split()[:3]
+                out.append((int(start), int(end), phone))
+    return out
+
+
 def _read_sphere(data, path):
     lines = data[:1024].split(b'\n')
     hdr_bytes = int(lines[1].strip())

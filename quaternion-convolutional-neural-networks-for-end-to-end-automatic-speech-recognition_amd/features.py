@@ -36,6 +36,43 @@ def num_frames(samples, sample_rate=16000, winlen=0.025, winstep=0.01):
     return 1 + int(math.ceil((1.0 * samples - frame_len) / frame_step))
 
 
+def frames_to_samples(frames, sample_rate=16000, winlen=0.025, winstep=0.01, position='centre'):
+    """Frame indices -> sample positions, in the geometry of frame_geometry: frame t starts at sample t * frame_step and covers
+    frame_len samples, so its centre is t * frame_step + frame_len // 2.  position='centre' (the default) gives the centre -- the
+    sample a frame-level boundary (functional.ctc_forced_align's starts / ends) stands for, and the inverse of samples_to_frames --
+    position='start' the first sample.  A negative frame index (the alignment's -1 for "none") gives -1.  `frames` is an int, an
+    integer numpy array or an integer torch tensor (device tensors stay on the device); the result has the same kind."""
+    if position not in ('centre', 'start'):
+        raise ValueError("frames_to_samples: position must be 'centre' or 'start', got %r" % (position,))
+    frame_len, frame_step = frame_geometry(sample_rate, winlen, winstep)
+    offset = frame_len // 2 if position == 'centre' else 0
+    if torch.is_tensor(frames):
+        f = frames.long()
+        return torch.where(f < 0, torch.full_like(f, -1), f * frame_step + offset)
+    if isinstance(frames, np.ndarray):
+        f = frames.astype(np.int64)
+        return np.where(f < 0, -1, f * frame_step + offset)
+    return -1 if frames < 0 else int(frames) * frame_step + offset
+
+
+def samples_to_frames(samples, sample_rate=16000, winlen=0.025, winstep=0.01):
+    """Sample positions -> frame indices, in the geometry of frame_geometry: a sample maps to the frame whose CENTRE
+    (t * frame_step + frame_len // 2) is nearest; a sample exactly half-way between two centres goes to the LOWER frame; the result
+    is clamped to >= 0 (samples in front of the first centre belong to frame 0).  It is not clamped from above: the caller knows the
+    utterance's frame count.  samples_to_frames(frames_to_samples(t)) == t for every t >= 0.  `samples` is an int, an integer numpy
+    array or an integer torch tensor; the result has the same kind."""
+    frame_len, frame_step = frame_geometry(sample_rate, winlen, winstep)
+    # ceil((d - step / 2) / step) with d = sample - centre of frame 0, in integers: -floor((step - 2 d) / (2 step))
+    if torch.is_tensor(samples):
+        d = samples.long() - frame_len // 2
+        return torch.clamp(-torch.div(frame_step - 2 * d, 2 * frame_step, rounding_mode='floor'), min=0)
+    if isinstance(samples, np.ndarray):
+        d = samples.astype(np.int64) - frame_len // 2
+        return np.maximum(-((frame_step - 2 * d) // (2 * frame_step)), 0)
+    d = int(samples) - frame_len // 2
+    return max(-((frame_step - 2 * d) // (2 * frame_step)), 0)
+
+
 def _mel_bins(nfilt, nfft, sample_rate, lowfreq, highfreq):
     lo, hi = (2595 * np.log10(1 + f / 700.) for f in (lowfreq, highfreq))
     mel = np.linspace(lo, hi, nfilt + 2)

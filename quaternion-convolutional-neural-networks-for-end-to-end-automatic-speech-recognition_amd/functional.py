@@ -9,6 +9,7 @@ PyTorch is plumbing here: it owns the device buffers (caching allocator), suppli
 current HIP stream and chains the backward calls.  There is NO CPU or eager fallback:
 a CPU tensor or a missing libqk_hip.so raises.
 """
+import collections
 import ctypes
 import math
 
@@ -1357,6 +1358,68 @@ def ctc_beam_search_decode(y_pred, input_length, beam_width=100, top_paths=1, me
                                                _ptr(dec), _ptr(dlen), _ptr(lp), _ptr(ws), n, _stream(y))
     L.check(rc, 'qk_ctc_beam_search_decode')
     return dec, dlen, lp
+
+
+# ---- CTC forced alignment (include/qk.h, "CTC forced alignment") ---------------------------------------------------------------------
+CTC_ALIGN_MAX_LABELS = 127
+AlignResult = collections.namedtuple('AlignResult', 'path starts ends score')
+
+
+def _length_arg(v, b, device, what, name):
+    """A (B,) or (B, 1) length argument, checked (shapes first: a bad shape is refused on any device) but not yet moved."""
+    if not torch.is_tensor(v):
+        v = torch.as_tensor(v)
+    if v.numel() != b or (v.dim() == 2 and v.shape[1] != 1) or v.dim() > 2:
+        raise ValueError('%s: %s must have shape (B,) or (B, 1), got %s' % (what, name, tuple(v.shape)))
+    if v.is_cuda and v.device != device:
+        raise ValueError('%s: %s is on %s, y_pred on %s' % (what, name, v.device, device))
+    return v.reshape(-1)
+
+
+def ctc_forced_align(y_pred, labels, input_length, label_length):
+    """The best CTC path of a known transcript, one launch (qk_ctc_forced_align): which frames belong to which label.  Arguments as
+    for ctc_batch_cost: y_pred (B, T, C) softmax outputs (float32 / bfloat16 / float16), blank = C - 1; labels (B, Lmax) int, Lmax <= 127
+    (Lmax = 0 is allowed); input_length, label_length (B,) or (B, 1).  Among the paths through blank, l1, blank, ..., lL, blank that
+    the alpha recursion allows, the one that maximises sum_t log_softmax(log(y_pred[t] + 1e-7))[class of the path at t] over the first
+    input_length[b] frames; ties: stay before s - 1 before s - 2, the final blank before the last label.
+
+    Returns AlignResult(path (B, T) int32: the class per frame, -1 behind input_length; starts, ends (B, Lmax) int32: first frame of
+    label i and one past its last, -1 behind label_length; score (B,) float32: the path's log-probability, <= -cost), device
+    tensors, without a host read.  A transcript that does not fit its frames gives score -inf and -1 everywhere."""
+    what = 'ctc_forced_align'
+    if y_pred.dim() != 3 or min(y_pred.shape) < 1:
+        raise ValueError('%s: y_pred must be a non-empty (B, T, C) tensor, got shape %s' % (what, tuple(y_pred.shape)))
+    b, t, c = y_pred.shape
+    if c < 2 or c > CTC_MAX_CLASSES:
+        raise ValueError('%s: %d classes; the alignment takes 2 <= classes <= %d' % (what, c, CTC_MAX_CLASSES))
+    if not torch.is_tensor(labels):
+        labels = torch.as_tensor(labels)
+    if labels.dim() != 2 or labels.shape[0] != b:
+        raise ValueError('%s: labels must have shape (B, Lmax) with B = %d, got %s' % (what, b, tuple(labels.shape)))
+    if labels.shape[1] > CTC_ALIGN_MAX_LABELS:
+        raise ValueError('%s: %d label slots; the alignment takes at most %d' % (what, labels.shape[1], CTC_ALIGN_MAX_LABELS))
+    if labels.is_cuda and labels.device != y_pred.device:
+        raise ValueError('%s: labels are on %s, y_pred on %s' % (what, labels.device, y_pred.device))
+    il = _length_arg(input_length, b, y_pred.device, what, 'input_length')
+    ll = _length_arg(label_length, b, y_pred.device, what, 'label_length')
+    _require_device(y_pred, what)
+    y = y_pred.contiguous()
+    il = il.to(device=y.device, dtype=torch.int32).contiguous()
+    ll = ll.to(device=y.device, dtype=torch.int32).contiguous()
+    lab = labels.to(device=y.device, dtype=torch.int32).contiguous()
+    lmax = lab.shape[1]
+    path = torch.empty((b, t), dtype=torch.int32, device=y.device)
+    starts = torch.empty((b, lmax), dtype=torch.int32, device=y.device)
+    ends = torch.empty((b, lmax), dtype=torch.int32, device=y.device)
+    score = torch.empty(b, dtype=torch.float32, device=y.device)
+    n = int(L.lib().qk_ctc_align_workspace_bytes(b, t, lmax))
+    ws = torch.empty(n, dtype=torch.uint8, device=y.device)
+    nz = lmax > 0
+    with _on_device(y.device):
+        rc = L.lib().qk_ctc_forced_align(_DTYPES[y.dtype], b, t, c, _ptr(y), _ptr(lab) if nz else None, lmax, _ptr(il), _ptr(ll), _ptr(path),
+                                         _ptr(starts) if nz else None, _ptr(ends) if nz else None, _ptr(score), _ptr(ws), n, _stream(y))
+    L.check(rc, 'qk_ctc_forced_align')
+    return AlignResult(path, starts, ends, score)
 
 
 CTC_LM_MAX_TRIGRAM_CLASSES = 64

@@ -457,6 +457,37 @@ def ctc_decode(y_pred, input_length, greedy=True, beam_width=100, top_paths=1, m
     return [dec[k, :, :int(n)].long() for k, n in enumerate(longest)], lp
 
 
+def ctc_align(y_pred, labels, input_length, label_length):
+    """Forced alignment of the transcripts to the posteriors on the device (functional.ctc_forced_align; semantics and the tie rule
+    are documented there and in include/qk.h, "CTC forced alignment").  Arguments as for ctc_batch_cost: y_pred (B, T, C) softmax
+    outputs, blank = C - 1; labels (B, Lmax); input_length, label_length (B,) or (B, 1).
+
+    Returns functional.AlignResult(path (B, T) int32, starts (B, Lmax) int32, ends (B, Lmax) int32, score (B,) float32): the class of
+    every frame (-1 behind input_length), the first frame of every label and one past its last (-1 behind label_length), and the
+    path's log-probability.  Device tensors, no host read; a transcript that does not fit gives score -inf and -1 everywhere."""
+    return Fq.ctc_forced_align(y_pred, labels, input_length, label_length)
+
+
+def boundary_agreement(starts, ref_starts, label_length, tolerance):
+    """Share of label boundaries an alignment places within `tolerance` of the reference (the TIMIT segmentation figure is the share
+    within 20 ms): a boundary is a hit when |starts[b][i] - ref_starts[b][i]| <= tolerance, counted for i < label_length[b] over
+    the feasible samples (an infeasible one has starts -1 at its first label and is left out).  starts, ref_starts (B, Lmax) in the
+    SAME unit (frames, or samples after features.frames_to_samples), label_length (B,) or (B, 1).
+    Returns (hits, total, share) as 0-dim device tensors (int64, int64, float32; 0 / 0 gives nan): plain torch ops, no host sync."""
+    if starts.dim() != 2 or ref_starts.shape != starts.shape:
+        raise ValueError('boundary_agreement: starts and ref_starts must both be (B, Lmax), got %s and %s'
+                         % (tuple(starts.shape), tuple(ref_starts.shape)))
+    ll = torch.as_tensor(label_length).reshape(-1).to(starts.device)
+    if ll.numel() != starts.shape[0]:
+        raise ValueError('boundary_agreement: label_length must have shape (B,) or (B, 1)')
+    ref = ref_starts.to(starts.device)
+    idx = torch.arange(starts.shape[1], device=starts.device)[None, :]
+    counted = (idx < ll[:, None]) & (starts >= 0)          # a feasible sample has no -1 in front of its label_length
+    hit = counted & ((starts.long() - ref.long()).abs() <= tolerance)
+    hits, total = hit.sum(), counted.sum()
+    return hits, total, hits.float() / total.float()
+
+
 def _seq_lengths(seq, length):
     if length is not None:
         return length

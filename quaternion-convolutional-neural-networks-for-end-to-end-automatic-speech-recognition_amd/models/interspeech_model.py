@@ -16,8 +16,8 @@ from .. import _lib as L
 from .. import functional as Fq
 from ..complexnn import QuaternionConv2D, QuaternionDense
 from ..keras_like import Layer, activations, regularizers
-from ..layers import (Dense, Dropout, MaxPooling2D, PReLU, TimeDistributed, ctc_batch_cost, ctc_decode, dense_softmax_ctc_mean,
-                      label_error_rate)
+from ..layers import (Dense, Dropout, MaxPooling2D, PReLU, TimeDistributed, ctc_align, ctc_batch_cost, ctc_decode,
+                      dense_softmax_ctc_mean, label_error_rate)
 
 # TimitQCNN.evaluate: mean CTC cost, edit operations and reference symbols summed over the batch, their ratio (the PER), the decodes
 EvalResult = collections.namedtuple('EvalResult', 'loss errors symbols per decoded log_prob')
@@ -276,6 +276,18 @@ class TimitQCNN(torch.nn.Module):
             il = input_length if input_length is not None else torch.full((y.shape[0],), y.shape[1], dtype=torch.int32, device=y.device)
             return ctc_decode(y, il, greedy=greedy, beam_width=beam_width, top_paths=top_paths, merge_repeated=merge_repeated, lm=lm,
                               lm_weight=lm_weight, insertion_bonus=insertion_bonus)
+        return self._inference(run)
+
+    def align(self, x, labels, input_length=None, label_length=None):
+        """Forced alignment of the transcripts `labels` (B, Lmax) to the eval-mode posteriors self(x): layers.ctc_align's
+        AlignResult(path (B, T), starts (B, Lmax), ends (B, Lmax), score (B,)) -- which frames the model gives to which phone.
+        input_length defaults to T for every sample, as in decode(); label_length defaults to Lmax for every sample."""
+        def run():
+            y = self(x)
+            il = input_length if input_length is not None else torch.full((y.shape[0],), y.shape[1], dtype=torch.int32, device=y.device)
+            ll = label_length if label_length is not None else torch.full((y.shape[0],), labels.shape[1], dtype=torch.int32,
+                                                                          device=y.device)
+            return ctc_align(y, labels, il, ll)
         return self._inference(run)
 
     def transcribe(self, wave, lengths=None, greedy=True, beam_width=100, top_paths=1, lm=None, lm_weight=0.5, insertion_bonus=0.0,
