@@ -33,6 +33,10 @@ measured with it.
 --align-eval adds to every evaluation the forced alignment of the held-out batch to its transcripts (TimitQCNN.align) and prints the
 share of phone boundaries it places within 20 ms of the hand-labelled ones in the .PHN files (a boundary is the centre of the
 phone's first frame, qcnn_amd.features.frames_to_samples).  Nobody has measured this figure for a trained model yet.
+
+--confusions N (0 = off) adds to every evaluation the split of the 39-class errors of ALL held-out batches into %cor / %sub / %del /
+%ins (of the reference phones, as sclite prints them; TimitQCNN.error_breakdown) and the N largest confusion pairs of the 39-class
+matrix, which is accumulated on the device over the batches (`<ins>` / `<del>` stand for the missing partner).
 """
 import argparse
 import fractions
@@ -46,7 +50,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
 import qcnn_amd  # noqa: E402,F401
 from qcnn_amd import dp, functional as F, layers  # noqa: E402
-from qcnn_amd.data import TIMIT_PHONES_61, read_audio, read_phn, read_phn_segments, timit_61_to_39_class_map  # noqa: E402
+from qcnn_amd.data import TIMIT_PHONES_39, TIMIT_PHONES_61, read_audio, read_phn, read_phn_segments, timit_61_to_39_class_map  # noqa: E402
 from qcnn_amd.features import SpecAugment, SpeedPerturb, frames_to_samples, quaternion_fbank  # noqa: E402
 from qcnn_amd.lm import NgramLM  # noqa: E402
 from qcnn_amd.models import getTimitModel2D  # noqa: E402
@@ -164,6 +168,8 @@ def main():
     ap.add_argument('--volume', type=parse_volume, default=(1.0, 1.0), help='speed perturbation: LO,HI of the linear gain drawn per utterance')
     ap.add_argument('--align-eval', action='store_true',
                     help='at every evaluation, force-align the held-out batch and print the share of boundaries within 20 ms of the .PHN ones')
+    ap.add_argument('--confusions', type=int, default=0, metavar='N',
+                    help='at every evaluation, print %%cor / %%sub / %%del / %%ins of all held-out batches and the top N confusion pairs (0 = off)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
@@ -175,7 +181,8 @@ def main():
         raise SystemExit('%s: no WAV / PHN pairs under TRAIN/' % args.timit)
     print('%d training and %d held-out utterances' % (len(train), len(test)))
     batches = length_batches(train, args.batch)
-    held_out = length_batches(test, args.batch)[0] if test else None
+    held_out_all = length_batches(test, args.batch) if test else []
+    held_out = held_out_all[0] if test else None
     class_map = torch.from_numpy(timit_61_to_39_class_map())
     lm = None
     if args.lm_order > 0:
@@ -237,6 +244,18 @@ def main():
                 hits, total, share = layers.boundary_agreement(frames_to_samples(ali.starts), reference_starts(test, held_out, le.shape[1], dev),
                                                                lle, tolerance=int(round(0.02 * 16000)))
                 print('step %5d  held-out boundary agreement within 20 ms %.4f (%d / %d)' % (step, float(share), int(hits), int(total)))
+            if args.confusions > 0:
+                confusion = torch.zeros((len(TIMIT_PHONES_39) + 1,) * 2, dtype=torch.int32, device=dev)
+                parts = []
+                for idx in held_out_all:                              # one matrix, accumulated on the device over the batches
+                    xb, ilb, lb, llb = to_device(test, idx, dev, dtype)
+                    parts.append(model.error_breakdown(xb, lb, ilb, llb, class_map=class_map, confusion=confusion))
+                c, s, d, i = (sum(int(getattr(p, f)) for p in parts) for f in ('correct', 'substitutions', 'deletions', 'insertions'))
+                n = max(c + s + d, 1)
+                print('step %5d  held-out %%cor %.2f  %%sub %.2f  %%del %.2f  %%ins %.2f  (%d reference phones, %d batches)'
+                      % (step, 100.0 * c / n, 100.0 * s / n, 100.0 * d / n, 100.0 * i / n, c + s + d, len(parts)))
+                for r, h, count in layers.top_confusions(confusion, args.confusions, TIMIT_PHONES_39):
+                    print('step %5d  confusion %-5s -> %-5s %d' % (step, r, h, count))
             if lm is not None:
                 plain = model.evaluate(xe, le, ile, lle, greedy=False, beam_width=args.beam_width, class_map=class_map)
                 fused = model.evaluate(xe, le, ile, lle, greedy=False, beam_width=args.beam_width, class_map=class_map, lm=lm,

@@ -471,6 +471,47 @@ int qk_ctc_beam_search_decode_lm(int32_t dtype, int32_t batch, int32_t frames, i
 int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
                      const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *distance, int32_t *ref_len_out, void *stream);
 
+/* ---- Scoring alignment ----------------------------------------------------------------------------------------------------------
+ * What sclite / compute-wer report beyond the distance: the split into correct, substituted, deleted and inserted tokens, the
+ * aligned reference / hypothesis pairs and the confusion matrix.  Inputs are those of qk_edit_distance: hyp (batch, hyp_stride),
+ * ref (batch, ref_stride) int32 with hyp_len, ref_len (batch) int32 clamped to [0, stride]; class_map (classes) int32 or NULL is
+ * applied to both sequences first: a token t in [0, classes) becomes class_map[t] and is dropped when that is negative, any other
+ * token passes through unchanged.  h_1..h_H and r_1..r_R are the sequences after the map.
+ *
+ * D[i][j] is the unit-cost Levenshtein distance between h_1..h_i and r_1..r_j.  The alignment is read backwards from (H, R) to
+ * (0, 0) under this tie rule, which is part of the definition (the result is bit-repeatable):
+ *   1. if i > 0, j > 0 and D[i][j] == D[i-1][j-1] + (h_i != r_j): the DIAGONAL -- correct when h_i == r_j, a substitution otherwise;
+ *   2. otherwise, if j > 0 and D[i][j] == D[i][j-1] + 1: a DELETION, r_j has no partner;
+ *   3. otherwise an INSERTION, h_i has no partner.
+ * Equivalently: of all minimum-cost alignments, read from the end, the smallest under diagonal < deletion < insertion.
+ *
+ * Outputs (caller-owned device memory; every element of every non-NULL output is written by every call, except confusion, which
+ * accumulates):
+ *   counts   (batch, 4) int32     correct, substitutions, deletions, insertions: C + S + D = R, C + S + I = H, S + D + I is the
+ *                                 distance of qk_edit_distance;
+ *   ali_ref, ali_hyp (batch, A) int32, A = hyp_stride + ref_stride   the aligned pairs in forward order, as mapped tokens;
+ *                                 ali_hyp = -1 marks a deletion, ali_ref = -1 an insertion; both -1 from ali_len[b] on;
+ *   ali_len  (batch) int32        the number of aligned pairs (<= H + R).
+ *                                 ali_ref, ali_hyp and ali_len are NULL together (the counts-only call) or not at all;
+ *   confusion ((K + 1), (K + 1)) int32 row-major, K = out_classes, or NULL   confusion[r][h] is INCREMENTED for every aligned
+ *                                 pair; row K holds the insertions, column K the deletions, [K][K] is never touched.  A pair with
+ *                                 a token outside [0, K) is left out of the matrix but still counted in counts.  The caller zeroes
+ *                                 the matrix once and accumulates over as many batches as wanted; integer adds keep the result
+ *                                 independent of the execution order.
+ *
+ * One wave per pair: the row sweep of qk_edit_distance, a 2-bit decision per cell packed by ballots (16 bytes per row and 64
+ * reference positions), one lane backtracks.  The decision table lives in LDS when the STRIDES (not the pair's own lengths) let
+ * the whole image fit in 64 KB, and in the workspace otherwise: qk_edit_align_workspace_bytes is 0 in the first case and
+ * batch * hyp_stride * 16 E bytes in the second (E = 1, 2, 4, 8, 17 for ref_stride < 64, 128, 256, 512, <= 1024); the workspace is
+ * 8-byte aligned and may be NULL when no bytes are needed.
+ * Limits: hyp_stride, ref_stride <= 1024 and, with confusion, out_classes <= 256: QK_ERR_UNSUPPORTED beyond.  Negative sizes and
+ * NULL required pointers: QK_ERR_INVALID_ARG.  Every such check happens before any pointer is touched.  batch == 0 returns 0
+ * without a launch.  Launches on `stream` and never synchronises. */
+size_t qk_edit_align_workspace_bytes(int32_t batch, int32_t hyp_stride, int32_t ref_stride);
+int qk_edit_align(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
+                  const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *counts, int32_t *ali_ref, int32_t *ali_hyp,
+                  int32_t *ali_len, int32_t *confusion, int32_t out_classes, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- CTC forced alignment ----------------------------------------------------------------------------------------------------
  * The best path of the CTC lattice of a KNOWN transcript: which frames belong to which label.  Inputs are those of
  * qk_ctc_batch_cost: y_pred (batch, frames, classes) softmax outputs in `dtype` (fp32, bf16 or fp16), blank = classes - 1; labels

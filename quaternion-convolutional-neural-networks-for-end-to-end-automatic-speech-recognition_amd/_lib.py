@@ -151,6 +151,8 @@ SYMBOLS = {
     'qk_ctc_beam_search_decode_lm': (ctypes.c_int, [I32, I32, I32, I32, _VP, _VP, I32, I32, I32, I32, _FP, ctypes.c_float,
                                                     ctypes.c_float, I32, _VP, _VP, _FP, _FP, _VP, _SZ, _VP]),
     'qk_edit_distance': (ctypes.c_int, [I32, _VP, I32, _VP, _VP, I32, _VP, _VP, I32, _VP, _VP, _VP]),
+    'qk_edit_align_workspace_bytes': (_SZ, [I32, I32, I32]),
+    'qk_edit_align': (ctypes.c_int, [I32, _VP, I32, _VP, _VP, I32, _VP, _VP, I32, _VP, _VP, _VP, _VP, _VP, I32, _VP, _SZ, _VP]),
     'qk_ctc_align_workspace_bytes': (_SZ, [I32, I32, I32]),
     'qk_ctc_forced_align': (ctypes.c_int, [I32, I32, I32, I32, _VP, _VP, I32, _VP, _VP, _VP, _VP, _VP, _FP, _VP, _SZ, _VP]),
     'qk_fbank_num_frames': (I32, [ctypes.c_int64, I32, I32]),

@@ -1137,6 +1137,40 @@ int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, cons
                                              distance, ref_len_out, (hipStream_t)stream), "qk_edit_distance");
 }
 
+size_t qk_edit_align_workspace_bytes(int32_t batch, int32_t hyp_stride, int32_t ref_stride)
+{
+    if (batch <= 0 || hyp_stride < 0 || ref_stride < 0 || hyp_stride > 1024 || ref_stride > 1024) return 0;
+    return edit_align_workspace_bytes(batch, hyp_stride, ref_stride);
+}
+
+int qk_edit_align(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
+                  const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *counts, int32_t *ali_ref, int32_t *ali_hyp,
+                  int32_t *ali_len, int32_t *confusion, int32_t out_classes, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (batch < 0 || hyp_stride < 0 || ref_stride < 0 || (class_map && classes <= 0) || (confusion && out_classes < 0)) {
+        set_error("edit_align: bad arguments (%d, %d, %d, %d, %d)", batch, hyp_stride, ref_stride, classes, out_classes); return QK_ERR_INVALID_ARG;
+    }
+    if (hyp_stride > 1024 || ref_stride > 1024 || (confusion && out_classes > 256)) {
+        set_error("edit_align: unsupported (hyp_stride %d <= 1024, ref_stride %d <= 1024, out_classes %d <= 256)", hyp_stride, ref_stride,
+                  confusion ? out_classes : 0);
+        return QK_ERR_UNSUPPORTED;
+    }
+    if (batch == 0) return 0;
+    if (!hyp_len || !ref_len || !counts || (hyp_stride > 0 && !hyp) || (ref_stride > 0 && !ref)) {
+        set_error("edit_align: NULL argument"); return QK_ERR_INVALID_ARG;
+    }
+    if ((ali_ref != nullptr) != (ali_hyp != nullptr) || (ali_ref != nullptr) != (ali_len != nullptr)) {
+        set_error("edit_align: ali_ref, ali_hyp and ali_len are NULL together or not at all"); return QK_ERR_INVALID_ARG;
+    }
+    const size_t need = edit_align_workspace_bytes(batch, hyp_stride, ref_stride);
+    if (need > 0 && (!workspace || workspace_bytes < need || !aligned(workspace, 8))) {
+        set_error("edit_align needs %zu workspace bytes (8-byte aligned), got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE;
+    }
+    return check_launch(launch_edit_align(batch, hyp, hyp_stride, hyp_len, ref, ref_stride, ref_len, class_map, class_map ? classes : 0,
+                                          counts, ali_ref, ali_hyp, ali_len, confusion, confusion ? out_classes : 0, workspace,
+                                          (hipStream_t)stream), "qk_edit_align");
+}
+
 size_t qk_ctc_align_workspace_bytes(int32_t batch, int32_t frames, int32_t max_label_len)
 {
     if (batch <= 0 || frames <= 0 || max_label_len < 0) return 0;

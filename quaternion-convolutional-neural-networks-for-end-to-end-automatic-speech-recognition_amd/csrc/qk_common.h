@@ -357,6 +357,11 @@ int launch_ctc_beam_lm(int dtype, int B, int T, int C, const void *pred, const i
                        hipStream_t stream);
 int launch_edit_distance(int B, const int *hyp, int hs, const int *hl, const int *ref, int rs, const int *rl, const int *cmap,
                          int classes, int *out, int *rlen_out, hipStream_t stream);
+// scoring alignment (qk_edit_align.hip): the decision table is in LDS or in the workspace, by the strides alone
+bool edit_align_table_in_lds(int hs, int rs);
+size_t edit_align_workspace_bytes(int B, int hs, int rs);
+int launch_edit_align(int B, const int *hyp, int hs, const int *hl, const int *ref, int rs, const int *rl, const int *cmap, int classes,
+                      int *counts, int *ali_ref, int *ali_hyp, int *ali_len, int *conf, int K, void *ws, hipStream_t stream);
 // CTC forced alignment (qk_ctc_align.hip)
 size_t ctc_align_workspace_bytes(int B, int T);
 bool ctc_align_supported(int T, int C, int Lmax);

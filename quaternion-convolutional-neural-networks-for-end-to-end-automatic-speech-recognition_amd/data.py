@@ -55,6 +55,20 @@ def timit_61_to_39_class_map():
     return cmap
 
 
+def _folded_names():
+    names = []
+    for p in TIMIT_PHONES_61:
+        folded = _FOLD_39.get(p, p)
+        if folded is not None and folded not in names:
+            names.append(folded)
+    return tuple(names)
+
+
+# The 39 folded names in the numbering of timit_61_to_39_class_map() (first appearance): the row / column names of a 39-class
+# confusion matrix (layers.top_confusions).
+TIMIT_PHONES_39 = _folded_names()
+
+
 def read_phn(path):
     """Phone names of a TIMIT .PHN file (lines `start end phone`), in order."""
     with open(path, 'r') as f:

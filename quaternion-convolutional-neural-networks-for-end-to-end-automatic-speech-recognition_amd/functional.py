@@ -1526,6 +1526,68 @@ def edit_distance(hyp, hyp_len, ref, ref_len, class_map=None):
     return _edit_distance(hyp, hyp_len, ref, ref_len, class_map)[0]
 
 
+# ---- Scoring alignment (include/qk.h, "Scoring alignment") ---------------------------------------------------------------------------
+EDIT_ALIGN_MAX_SEQ = 1024
+EDIT_ALIGN_MAX_CLASSES = 256
+EditAlignment = collections.namedtuple('EditAlignment', 'ref hyp length counts')
+
+
+def edit_alignment(hyp, hyp_len, ref, ref_len, class_map=None, confusion=None, align=True):
+    """The Levenshtein alignment behind edit_distance, one launch (qk_edit_align): hyp (B, Lh), ref (B, Lr) device int tensors with
+    Lh, Lr <= 1024, hyp_len / ref_len (B,), class_map as in edit_distance.  Read backwards from the end, the alignment takes the
+    diagonal (correct or substitution) when it is optimal, otherwise a deletion when that is optimal, otherwise an insertion.
+
+    Returns EditAlignment(ref, hyp (B, Lh + Lr) int32: the aligned pairs in forward order as mapped tokens, hyp = -1 a deletion,
+    ref = -1 an insertion, both -1 behind length; length (B,) int32; counts (B, 4) int32: correct, substitutions, deletions,
+    insertions), device tensors, without a host read.  align=False is the counts-only call: ref, hyp and length are None.
+    confusion: a caller-owned (K + 1, K + 1) int32 contiguous tensor on the same device, ACCUMULATED in place: [r][h] += 1 per
+    aligned pair, row K the insertions, column K the deletions; pairs with a token outside [0, K) are counted but left out of it."""
+    what = 'edit_alignment'
+    # shapes first (a bad shape is refused on any device), then the device
+    if torch.is_tensor(hyp) and torch.is_tensor(ref) and hyp.dim() == 2 and ref.dim() == 2:
+        if hyp.shape[0] != ref.shape[0]:
+            raise ValueError('%s: %d hypotheses, %d references' % (what, hyp.shape[0], ref.shape[0]))
+        if max(hyp.shape[1], ref.shape[1]) > EDIT_ALIGN_MAX_SEQ:
+            raise ValueError('%s: sequences of up to %d tokens are supported, got hyp %d, ref %d' % (what, EDIT_ALIGN_MAX_SEQ, hyp.shape[1],
+                                                                                                     ref.shape[1]))
+    k = 0
+    if confusion is not None:
+        if (not torch.is_tensor(confusion) or confusion.dim() != 2 or confusion.shape[0] != confusion.shape[1] or confusion.shape[0] < 1
+                or confusion.dtype != torch.int32 or not confusion.is_contiguous()):
+            raise ValueError('%s: confusion must be a square (K + 1, K + 1) int32 contiguous tensor' % what)
+        k = confusion.shape[0] - 1
+        if k > EDIT_ALIGN_MAX_CLASSES:
+            raise ValueError('%s: a confusion matrix of up to %d classes is supported, got %d' % (what, EDIT_ALIGN_MAX_CLASSES, k))
+    h, hl = _token_args(hyp, hyp_len, what, 'hyp')
+    r, rl = _token_args(ref, ref_len, what, 'ref')
+    if h.device != r.device:
+        raise ValueError('%s: hyp on %s, ref on %s' % (what, h.device, r.device))
+    if confusion is not None and confusion.device != h.device:
+        raise ValueError('%s: confusion on %s, hyp on %s' % (what, confusion.device, h.device))
+    b, a = h.shape[0], h.shape[1] + r.shape[1]
+    cm, classes = None, 0
+    if class_map is not None:
+        cm = torch.as_tensor(class_map).reshape(-1).to(device=h.device, dtype=torch.int32).contiguous()
+        classes = cm.numel()
+        if classes < 1:
+            raise ValueError('%s: empty class_map' % what)
+    counts = torch.empty((b, 4), dtype=torch.int32, device=h.device)
+    ali_ref = ali_hyp = ali_len = None
+    if align:
+        ali_ref = torch.empty((b, a), dtype=torch.int32, device=h.device)
+        ali_hyp = torch.empty((b, a), dtype=torch.int32, device=h.device)
+        ali_len = torch.empty(b, dtype=torch.int32, device=h.device)
+    if b == 0:
+        return EditAlignment(ali_ref, ali_hyp, ali_len, counts)
+    n = int(L.lib().qk_edit_align_workspace_bytes(b, h.shape[1], r.shape[1]))
+    ws = torch.empty(n, dtype=torch.uint8, device=h.device) if n else None
+    with _on_device(h.device):
+        rc = L.lib().qk_edit_align(b, _ptr(h), h.shape[1], _ptr(hl), _ptr(r), r.shape[1], _ptr(rl), _ptr(cm), classes, _ptr(counts),
+                                   _ptr(ali_ref), _ptr(ali_hyp), _ptr(ali_len), _ptr(confusion), k, _ptr(ws), n, _stream(h))
+    L.check(rc, 'qk_edit_align')
+    return EditAlignment(ali_ref, ali_hyp, ali_len, counts)
+
+
 # ---- Acoustic front end (include/qk.h, "Acoustic front end") -------------------------------------------------------------------
 def fbank_quaternion(wave, lengths, frames, frame_len, frame_step, nfft, preemph, window, mel_bins, append_energy, delta_n, normalize,
                      dtype):

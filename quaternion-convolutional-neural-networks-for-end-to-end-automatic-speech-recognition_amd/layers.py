@@ -10,6 +10,8 @@ torch ops with the Keras/TensorFlow semantics the models rely on (SURVEY.md 8f r
     (B, 4F, 41, T) tensor this pools the 41-bin frequency axis 41 -> 14).
 """
 
+import collections
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -515,3 +517,43 @@ def label_error_rate(decoded, decoded_len, labels, label_length, class_map=None)
     dist, rlen = Fq._edit_distance(decoded, _seq_lengths(decoded, decoded_len), labels, label_length, class_map)
     errors, symbols = dist.long().sum(), rlen.long().sum()
     return errors, symbols, errors.float() / symbols.float()
+
+
+# label_error_rate's single figure split the way scoring tools print it
+ErrorBreakdown = collections.namedtuple('ErrorBreakdown', 'correct substitutions deletions insertions symbols per')
+
+
+def error_breakdown(decoded, decoded_len, labels, label_length, class_map=None, confusion=None):
+    """label_error_rate split into its parts (functional.edit_alignment, counts only): ErrorBreakdown(correct, substitutions,
+    deletions, insertions, symbols, per) summed over the batch, 0-dim device tensors (int64; per float32) without a host sync.
+    symbols = correct + substitutions + deletions is the number of reference labels after the optional class_map, and
+    per = (S + D + I) / max(symbols, 1) is label_error_rate's on the same inputs.  The split follows the tie rule of include/qk.h,
+    "Scoring alignment".  decoded_len=None means -1-padded rows.  confusion: a (K + 1, K + 1) int32 device tensor the aligned pairs
+    are added to (row K insertions, column K deletions); zero it once and pass it for every batch."""
+    if torch.is_tensor(labels) and torch.is_tensor(decoded):
+        labels = labels.to(decoded.device)
+    res = Fq.edit_alignment(decoded, _seq_lengths(decoded, decoded_len), labels, label_length, class_map, confusion=confusion, align=False)
+    c, s, d, i = res.counts.long().sum(dim=0).unbind()
+    symbols = c + s + d
+    return ErrorBreakdown(c, s, d, i, symbols, (s + d + i).float() / symbols.clamp(min=1).float())
+
+
+def top_confusions(confusion, k=10, names=None):
+    """The k largest off-diagonal entries of a confusion matrix filled by error_breakdown / functional.edit_alignment, as
+    [(ref, hyp, count)] sorted by falling count, ties by (ref, hyp); zero entries are left out.  A host helper: it reads the matrix
+    once.  Index K (an insertion's ref, a deletion's hyp) is rendered as None, or as '<ins>' / '<del>' when `names` (K strings)
+    turns the other indices into names."""
+    m = np.asarray(confusion.cpu() if torch.is_tensor(confusion) else confusion)
+    if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:
+        raise ValueError('top_confusions: a square (K + 1, K + 1) matrix is needed, got shape %s' % (tuple(m.shape),))
+    kk = m.shape[0] - 1
+    if names is not None and len(names) != kk:
+        raise ValueError('top_confusions: %d names for %d classes' % (len(names), kk))
+    entries = [(-int(m[r, h]), r, h) for r in range(kk + 1) for h in range(kk + 1) if r != h and m[r, h] > 0]
+    out = []
+    for neg, r, h in sorted(entries)[:max(int(k), 0)]:
+        if names is None:
+            out.append((None if r == kk else r, None if h == kk else h, -neg))
+        else:
+            out.append(('<ins>' if r == kk else names[r], '<del>' if h == kk else names[h], -neg))
+    return out

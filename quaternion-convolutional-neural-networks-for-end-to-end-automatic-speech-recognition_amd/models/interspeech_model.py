@@ -17,7 +17,7 @@ from .. import functional as Fq
 from ..complexnn import QuaternionConv2D, QuaternionDense
 from ..keras_like import Layer, activations, regularizers
 from ..layers import (Dense, Dropout, MaxPooling2D, PReLU, TimeDistributed, ctc_align, ctc_batch_cost, ctc_decode,
-                      dense_softmax_ctc_mean, label_error_rate)
+                      dense_softmax_ctc_mean, error_breakdown, label_error_rate)
 
 # TimitQCNN.evaluate: mean CTC cost, edit operations and reference symbols summed over the batch, their ratio (the PER), the decodes
 EvalResult = collections.namedtuple('EvalResult', 'loss errors symbols per decoded log_prob')
@@ -320,6 +320,21 @@ class TimitQCNN(torch.nn.Module):
                                            lm_weight=lm_weight, insertion_bonus=insertion_bonus)
             errors, symbols, per = label_error_rate(decoded[0], None, labels, label_length, class_map)
             return EvalResult(loss, errors, symbols, per, decoded[0], log_prob)
+        return self._inference(run)
+
+    def error_breakdown(self, x, labels, input_length, label_length, greedy=True, beam_width=100, class_map=None, lm=None, lm_weight=0.5,
+                        insertion_bonus=0.0, confusion=None):
+        """evaluate()'s PER split into its parts, from one eval-mode forward: the decode of decode() scored by
+        layers.error_breakdown -- ErrorBreakdown(correct, substitutions, deletions, insertions, symbols, per), device tensors
+        summed over the batch; per equals evaluate(...).per.  confusion: a (K + 1, K + 1) int32 device tensor the aligned pairs are
+        added to (K = 39 with the TIMIT class_map); zero it once and pass it for every batch."""
+        if lm is not None and greedy:
+            raise ValueError('error_breakdown: a language model needs the beam search (greedy=False)')
+
+        def run():
+            decoded, _ = ctc_decode(self(x), input_length, greedy=greedy, beam_width=beam_width, top_paths=1, lm=lm, lm_weight=lm_weight,
+                                    insertion_bonus=insertion_bonus)
+            return error_breakdown(decoded[0], None, labels, label_length, class_map, confusion=confusion)
         return self._inference(run)
 
     def regularization_loss(self):
