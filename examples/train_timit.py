@@ -30,6 +30,14 @@ filter bank (qcnn_amd.features.SpeedPerturb, one launch, seeded from --seed).  T
 fewer frames for the same labels.  Evaluation batches are never perturbed; it combines with --specaug.  No phone error rate has been
 measured with it.
 
+--noise-reverb convolves, with probability --rir-prob (default 0.5), every utterance of a TRAINING batch with a room impulse response
+and adds, with probability --noise-prob (default 0.5), a noise recording at a signal-to-noise ratio drawn from --snr LO,HI dB (default
+5,20), on the device behind --speed-perturb and in front of the filter bank (qcnn_amd.features.NoiseReverb, two launches, seeded from
+--seed).  --rir-dir DIR / --noise-dir DIR name directories of audio files (any format qcnn_amd.data.read_audio reads; walked
+recursively); without them synthetic banks are used (qcnn_amd.features.synthetic_rirs / synthetic_noises).  Lengths and labels are
+unchanged.  Evaluation batches are never corrupted; it combines with --speed-perturb and --specaug.  No phone error rate has been
+measured with it.
+
 --align-eval adds to every evaluation the forced alignment of the held-out batch to its transcripts (TimitQCNN.align) and prints the
 share of phone boundaries it places within 20 ms of the hand-labelled ones in the .PHN files (a boundary is the centre of the
 phone's first frame, qcnn_amd.features.frames_to_samples).  Nobody has measured this figure for a trained model yet.
@@ -51,7 +59,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
 import qcnn_amd  # noqa: E402,F401
 from qcnn_amd import dp, functional as F, layers  # noqa: E402
 from qcnn_amd.data import TIMIT_PHONES_39, TIMIT_PHONES_61, read_audio, read_phn, read_phn_segments, timit_61_to_39_class_map  # noqa: E402
-from qcnn_amd.features import SpecAugment, SpeedPerturb, frames_to_samples, quaternion_fbank  # noqa: E402
+from qcnn_amd.features import (NoiseReverb, SpecAugment, SpeedPerturb, frames_to_samples, quaternion_fbank, synthetic_noises,  # noqa: E402
+                               synthetic_rirs)
 from qcnn_amd.lm import NgramLM  # noqa: E402
 from qcnn_amd.models import getTimitModel2D  # noqa: E402
 from qcnn_amd.training import GradGuard  # noqa: E402
@@ -107,9 +116,25 @@ def parse_volume(text):
     return lo, hi
 
 
+def read_audio_dir(root, what):
+    """Every audio file under `root` that read_audio can read, as a list of 1-D arrays (sorted by path)."""
+    out = []
+    for d, _, files in sorted(os.walk(root)):
+        for f in sorted(files):
+            try:
+                wav = np.asarray(read_audio(os.path.join(d, f)))
+            except (ValueError, OSError):
+                continue
+            if wav.ndim == 1 and wav.size:
+                out.append(wav)
+    if not out:
+        raise SystemExit('%s: no readable audio file for the %s bank' % (root, what))
+    return out
+
+
 def to_device(utts, idx, dev, dtype, augment=None, wave_augment=None):
-    """Features (quaternion_fbank, per-utterance normalisation; SpeedPerturb on the waveforms when `wave_augment` is given and
-    SpecAugment when `augment` is: training batches only), frame counts, padded labels and label lengths of one batch."""
+    """Features (quaternion_fbank, per-utterance normalisation; the waveform policies of `wave_augment` -- SpeedPerturb, NoiseReverb
+    -- when given and SpecAugment when `augment` is: training batches only), frame counts, padded labels and label lengths of one batch."""
     n = [len(utts[i][0]) for i in idx]
     wave = np.zeros((len(idx), max(n)), dtype=np.int16)
     lab_len = [len(utts[i][1]) for i in idx]
@@ -166,6 +191,13 @@ def main():
     ap.add_argument('--speeds', type=parse_speeds, default=((9, 10), (1, 1), (11, 10)),
                     help='speed perturbation: comma-separated speeds, each taken as a fraction with a denominator <= 32')
     ap.add_argument('--volume', type=parse_volume, default=(1.0, 1.0), help='speed perturbation: LO,HI of the linear gain drawn per utterance')
+    ap.add_argument('--noise-reverb', action='store_true',
+                    help='reverberation and additive noise on the training waveforms (never on evaluation batches), behind --speed-perturb')
+    ap.add_argument('--rir-dir', default=None, help='noise-reverb: directory of room impulse responses (default: synthetic ones)')
+    ap.add_argument('--noise-dir', default=None, help='noise-reverb: directory of noise recordings (default: synthetic ones)')
+    ap.add_argument('--rir-prob', type=float, default=0.5, help='noise-reverb: probability of reverberating an utterance')
+    ap.add_argument('--noise-prob', type=float, default=0.5, help='noise-reverb: probability of adding noise to an utterance')
+    ap.add_argument('--snr', type=parse_volume, default=(5.0, 20.0), help='noise-reverb: LO,HI of the signal-to-noise ratio in dB')
     ap.add_argument('--align-eval', action='store_true',
                     help='at every evaluation, force-align the held-out batch and print the share of boundaries within 20 ms of the .PHN ones')
     ap.add_argument('--confusions', type=int, default=0, metavar='N',
@@ -210,6 +242,12 @@ def main():
     wave_augment = None
     if args.speed_perturb:
         wave_augment = SpeedPerturb(speeds=args.speeds, gain=args.volume, seed=args.seed & 0xFFFFFFFF)
+    if args.noise_reverb:
+        rirs = [np.asarray(h, dtype=np.float64) for h in read_audio_dir(args.rir_dir, 'rir')] if args.rir_dir else synthetic_rirs(32, seed=args.seed & 0xFFFFFFFF)
+        noises = read_audio_dir(args.noise_dir, 'noise') if args.noise_dir else synthetic_noises(8, 64000, seed=args.seed & 0xFFFFFFFF)
+        noise_reverb = NoiseReverb(rirs=F.prepare_rirs(rirs, device=dev), noises=F.prepare_noises(noises, device=dev),
+                                   rir_prob=args.rir_prob, noise_prob=args.noise_prob, snr=args.snr, seed=args.seed & 0xFFFFFFFF)
+        wave_augment = noise_reverb if wave_augment is None else (wave_augment, noise_reverb)
     # clipping / float16 / dynamic scaling: the guarded step (qcnn_amd.training.GradGuard).  Norm, overflow check, clip and scale
     # update all happen on the device, and so does the step count (a skipped step does not advance it).
     guard = None

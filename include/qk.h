@@ -682,6 +682,77 @@ int qk_speed_perturb(int32_t wave_dtype, int32_t batch, int64_t max_samples, con
                      const qk_speed_perturb_t *policy, const float *tables /* device */, const uint32_t *counter_dev /* NULL: 0 */,
                      int64_t out_samples, float *out, int32_t *out_lengths, int32_t *plan /* (batch, 4) or NULL */, void *stream);
 
+/* ---- Reverberation and additive noise ---------------------------------------------------------------------------------------
+ * The environmental corruption of Kaldi's `wav-reverberate` (Ko et al., 2017, "A study on data augmentation of reverberant speech
+ * for robust speech recognition"), in front of qk_fbank_quaternion and behind qk_speed_perturb: every utterance is, with
+ * probability rir_prob, convolved with one room impulse response of a bank, and gets, with probability noise_prob, one recording
+ * of a noise bank added at a signal-to-noise ratio drawn from [snr_lo, snr_hi) dB.  wave is a contiguous (batch, max_samples)
+ * matrix of wave_dtype (QK_WAVE_I16 or QK_WAVE_F32), lengths (batch) int32 the valid samples per row; out is a contiguous
+ * (batch, max_samples) fp32 matrix at the input's scale.  The length of an utterance does not change: there is no out_lengths.
+ * rirs is a (n_rirs, rir_stride) fp32 matrix on the device, row i holding rir_len[i] taps whose direct path is tap rir_delay[i];
+ * noises a (n_noises, noise_stride) fp32 matrix, row i holding noise_len[i] samples; rows need 4-byte alignment only.  The call
+ * is at most three launches on `stream` (two here: the filter with the energy partials, then the gain and the mix; the second is
+ * left out when no noise can fire), reads nothing on the host, does not synchronise and uses no atomics, so it captures into a
+ * graph; the draws are the counter-based hash of the SpecAugment section: bit-repeatable from (seed, *counter_dev), and new on
+ * every replay of a captured graph whose counter a device op advances.  Seeds of data-parallel ranks: as for SpecAugment.
+ * Utterances whose do_rir is false do no convolution work.  The caller owns the workspace (qk_noise_reverb_workspace_bytes,
+ * 8-byte aligned): it holds the float64 energy partials of every tile of every utterance; r lives in `out` between the launches.
+ *
+ * Per utterance b, with n = clamp(lengths[b], 0, max_samples):
+ * Draws: fmix, key, u(b,k) and randint(b,k,m) exactly as in the SpecAugment section, with draw indices k = 72 .. 77 (0 .. 33 and
+ *   64, 65 are taken by SpecAugment and the speed perturbation):
+ *   do_rir = n_rirs > 0 && (u(b,72) >> 8) < rir_prob_q24;        ri = randint(b,73, n_rirs)
+ *   do_noise = n_noises > 0 && (u(b,74) >> 8) < noise_prob_q24;  ni = randint(b,75, n_noises);  o = randint(b,76, noise_len[ni])
+ *   f = float(u(b,77) >> 8) * 2^-24 (exact, in [0, 1));  snr = snr_lo + (snr_hi - snr_lo) * f in fp32: the difference, the product
+ *   and the sum are each rounded once (no fused multiply-add), so snr_lo == snr_hi gives exactly that value.
+ *   The probabilities are integers in 0 .. 2^24 (probability p: round(p 2^24)); 2^24 always fires, 0 never does.
+ * Reverberation: h = rirs + ri * rir_stride, Lr = rir_len[ri], d = rir_delay[ri].  For 0 <= m < n:
+ *   r[m] = sum_{j=0}^{Lr-1} h[j] * x[b, m + d - j], with x taken as 0 outside [0, n): sample m of the output lines up with sample m
+ *   of the input through the direct path, so the labels keep their places.  Products and sums are fp32, in any order, fused or
+ *   not (the sum starts from +0, and taps beyond Lr enter as zeros: a -0 may come out as +0, and x must be finite).
+ *   do_rir false: r[m] = float(x[b, m]), a bit copy for fp32 input.
+ * Noise: v[m] = noises[ni * noise_stride + (o + m) % noise_len[ni]] -- the recording starts at o and wraps around.
+ *   Es = sum_{m<n} r[m]^2, En = sum_{m<n} v[m]^2: the fp32 values are squared and summed in float64, in a fixed order.
+ *   a = float(sqrt(Es / En) * 10^(-snr / 20)), evaluated in float64 and rounded once; a = 0 when En == 0 or Es == 0.
+ *   out[b, m] = r[m] + a * v[m]: one fp32 product and one fp32 sum, or one fused multiply-add (a == 0: out = r, v is not read).
+ *   do_noise false: out = r.
+ * out[b, m] = +0 for n <= m < max_samples.
+ * Containment: nothing from an input sample >= n reaches the output, whatever it holds (NaN included), and nothing at or beyond
+ *   rir_len[i] / noise_len[i] of a bank row is ever read.
+ * Plan row (plan: (batch, QK_NOISE_REVERB_PLAN_WORDS) int32, or NULL): {n, do_rir ? ri : -1, do_noise ? ni : -1, o, the bits of
+ *   snr, the bits of a, the bits of float(Es), the bits of float(En)}; o, a, Es and En are 0 when do_noise is false.
+ * Decided on the host, before anything touches the device --
+ * QK_ERR_INVALID_ARG: a NULL wave / lengths / policy / out / workspace; batch or max_samples < 1; a wave_dtype other than the two;
+ *   a negative n_rirs or n_noises; rirs / rir_len / rir_delay NULL while n_rirs > 0, noises / noise_len NULL while n_noises > 0;
+ *   rir_stride or noise_stride < 1 (an empty bank gives 1); a probability outside 0 .. 2^24; snr bounds not finite or snr_lo > snr_hi; out
+ *   overlapping wave; workspace_bytes below qk_noise_reverb_workspace_bytes; a pointer not aligned to its element size (the
+ *   workspace: 8 bytes).
+ * QK_ERR_UNSUPPORTED: rir_stride > QK_REVERB_MAX_TAPS; max_samples >= 2^26.
+ * NOT checked -- they live on the device, and are the caller's duty (qcnn_amd.functional.prepare_rirs / prepare_noises guarantee
+ *   them): rir_len[i] in 1 .. rir_stride, rir_delay[i] in 0 .. rir_len[i] - 1, noise_len[i] in 1 .. noise_stride.  The kernels
+ *   clamp what they read into these ranges, so a bad bank gives a wrong signal, not a stray read.
+ * qk_noise_reverb_workspace_bytes: known without reading anything from the device; -1 for batch < 1, max_samples < 1 or
+ *   max_samples >= 2^26. */
+#define QK_REVERB_MAX_TAPS 8192
+#define QK_NOISE_REVERB_PLAN_WORDS 8
+typedef struct qk_noise_reverb_t {
+    int32_t n_rirs;                                /* rows of `rirs`; 0: no reverberation */
+    int32_t rir_stride;                            /* floats per row of `rirs`, 1 .. QK_REVERB_MAX_TAPS */
+    int32_t n_noises;                              /* rows of `noises`; 0: no noise */
+    int32_t noise_stride;                          /* floats per row of `noises` */
+    int32_t rir_prob_q24;                          /* probability of reverberation times 2^24, in 0 .. 2^24 */
+    int32_t noise_prob_q24;                        /* probability of noise times 2^24, in 0 .. 2^24 */
+    float snr_lo, snr_hi;                          /* signal-to-noise ratio in dB, drawn from [snr_lo, snr_hi); lo == hi: constant */
+    uint32_t seed;
+} qk_noise_reverb_t;
+int64_t qk_noise_reverb_workspace_bytes(int32_t batch, int64_t max_samples);
+int qk_noise_reverb(int32_t wave_dtype, int32_t batch, int64_t max_samples, const void *wave, const int32_t *lengths,
+                    const qk_noise_reverb_t *policy,
+                    const float *rirs, const int32_t *rir_len, const int32_t *rir_delay,      /* device; NULL when n_rirs == 0 */
+                    const float *noises, const int32_t *noise_len,                            /* device; NULL when n_noises == 0 */
+                    const uint32_t *counter_dev /* NULL: 0 */, float *out, int32_t *plan /* (batch, 8) or NULL */,
+                    void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Softmax over the last axis of a (rows, cols <= 64) matrix, one wave per row -- the activation of the model's
  * TimeDistributed(Dense(62, activation='softmax')) output layer (models/interspeech_model.py:171-175) and its autodiff:
  *   fwd   y = softmax(logits + bias)          logits: fp32 (the GEMM's fp32 output), bias: fp32 or NULL, y: `dtype`

@@ -32,6 +32,7 @@ QK_FBANK_NORM_NONE, QK_FBANK_NORM_UTTERANCE = 0, 1
 QK_FBANK_MAX_FILT = 128
 QK_SPECAUG_MAX_MASKS, QK_SPECAUG_PLAN_WORDS = 8, 36             # SpecAugment (qk_spec_augment)
 QK_SPEED_MAX_SPEEDS, QK_SPEED_MAX_DEN, QK_SPEED_MAX_TAPS, QK_SPEED_PLAN_WORDS = 8, 32, 64, 4       # qk_speed_perturb
+QK_REVERB_MAX_TAPS, QK_NOISE_REVERB_PLAN_WORDS = 8192, 8                                          # qk_noise_reverb
 QK_ERR_INVALID_ARG, QK_ERR_UNSUPPORTED, QK_ERR_WORKSPACE, QK_ERR_LAUNCH = -1, -2, -3, -4
 QK_PATH_NAMES = {0: 'none', 1: 'mfma16', 2: 'mfma16_band', 3: 'fp32_mfma', 4: 'mfma16_point', 5: 'mfma16_small'}               # qk_last_path
 
@@ -94,6 +95,12 @@ class SpeedPerturbPolicy(ctypes.Structure):
     """qk_speed_perturb_t (include/qk.h)"""
     _fields_ = [('n_speeds', I32), ('num', I32 * 8), ('den', I32 * 8), ('half_width', I32 * 8), ('table_offset', I32 * 8),
                 ('gain_lo', ctypes.c_float), ('gain_hi', ctypes.c_float), ('seed', ctypes.c_uint32)]
+
+
+class NoiseReverbPolicy(ctypes.Structure):
+    """qk_noise_reverb_t (include/qk.h)"""
+    _fields_ = [('n_rirs', I32), ('rir_stride', I32), ('n_noises', I32), ('noise_stride', I32), ('rir_prob_q24', I32),
+                ('noise_prob_q24', I32), ('snr_lo', ctypes.c_float), ('snr_hi', ctypes.c_float), ('seed', ctypes.c_uint32)]
 
 
 # qk_grad_guard_state_t: eight 4-byte fields in device memory; (name, is_float) in order
@@ -163,6 +170,9 @@ SYMBOLS = {
     'qk_speed_perturb_out_samples': (ctypes.c_int64, [ctypes.c_int64, ctypes.POINTER(SpeedPerturbPolicy)]),
     'qk_speed_perturb': (ctypes.c_int, [I32, I32, ctypes.c_int64, _VP, _VP, ctypes.POINTER(SpeedPerturbPolicy), _VP, _VP, ctypes.c_int64,
                                         _VP, _VP, _VP, _VP]),
+    'qk_noise_reverb_workspace_bytes': (ctypes.c_int64, [I32, ctypes.c_int64]),
+    'qk_noise_reverb': (ctypes.c_int, [I32, I32, ctypes.c_int64, _VP, _VP, ctypes.POINTER(NoiseReverbPolicy), _VP, _VP, _VP, _VP, _VP, _VP,
+                                       _VP, _VP, _VP, ctypes.c_int64, _VP]),
     'qk_softmax_rows_fwd': (ctypes.c_int, [I32, ctypes.c_int64, I32, _VP, _VP, _VP, _VP]),
     'qk_softmax_rows_bwd': (ctypes.c_int, [I32, ctypes.c_int64, I32, _VP, _VP, _VP, _VP, _VP]),
     'qk_dense_softmax_supported': (ctypes.c_int, [I32, ctypes.c_int64, I32, I32]),

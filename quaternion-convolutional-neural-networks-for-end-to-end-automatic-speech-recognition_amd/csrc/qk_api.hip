@@ -1380,6 +1380,60 @@ int qk_speed_perturb(int32_t wave_dtype, int32_t batch, int64_t max_samples, con
                                              out, out_lengths, plan, (hipStream_t)stream), "qk_speed_perturb");
 }
 
+int64_t qk_noise_reverb_workspace_bytes(int32_t batch, int64_t max_samples)
+{
+    if (batch < 1 || max_samples < 1 || max_samples >= ((int64_t)1 << 26)) {
+        set_error("noise_reverb_workspace_bytes: batch %d, max_samples %lld (1 .. 2^26 - 1)", batch, (long long)max_samples); return -1;
+    }
+    return (int64_t)noise_reverb_workspace_bytes(batch, (int)max_samples);
+}
+
+int qk_noise_reverb(int32_t wave_dtype, int32_t batch, int64_t max_samples, const void *wave, const int32_t *lengths,
+                    const qk_noise_reverb_t *policy, const float *rirs, const int32_t *rir_len, const int32_t *rir_delay,
+                    const float *noises, const int32_t *noise_len, const uint32_t *counter_dev, float *out, int32_t *plan,
+                    void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (batch < 1 || max_samples < 1 || (wave_dtype != QK_WAVE_F32 && wave_dtype != QK_WAVE_I16)) {
+        set_error("noise_reverb: bad arguments (batch %d, max_samples %lld, wave_dtype %d)", batch, (long long)max_samples, wave_dtype);
+        return QK_ERR_INVALID_ARG;
+    }
+    if (!wave || !lengths || !policy || !out || !workspace) { set_error("noise_reverb: NULL argument"); return QK_ERR_INVALID_ARG; }
+    const qk_noise_reverb_t &p = *policy;
+    if (p.n_rirs < 0 || p.n_noises < 0) { set_error("noise_reverb: n_rirs %d / n_noises %d negative", p.n_rirs, p.n_noises); return QK_ERR_INVALID_ARG; }
+    if (p.n_rirs > 0 && (!rirs || !rir_len || !rir_delay)) { set_error("noise_reverb: rirs / rir_len / rir_delay is NULL with n_rirs %d", p.n_rirs); return QK_ERR_INVALID_ARG; }
+    if (p.n_noises > 0 && (!noises || !noise_len)) { set_error("noise_reverb: noises / noise_len is NULL with n_noises %d", p.n_noises); return QK_ERR_INVALID_ARG; }
+    if (p.rir_stride < 1 || p.noise_stride < 1) { set_error("noise_reverb: rir_stride %d / noise_stride %d < 1", p.rir_stride, p.noise_stride); return QK_ERR_INVALID_ARG; }
+    const int one = 1 << 24;
+    if (p.rir_prob_q24 < 0 || p.rir_prob_q24 > one || p.noise_prob_q24 < 0 || p.noise_prob_q24 > one) {
+        set_error("noise_reverb: probabilities %d, %d outside 0 .. 2^24", p.rir_prob_q24, p.noise_prob_q24); return QK_ERR_INVALID_ARG;
+    }
+    if (!isfinite(p.snr_lo) || !isfinite(p.snr_hi) || p.snr_lo > p.snr_hi) {
+        set_error("noise_reverb: snr bounds %g, %g must be finite with snr_lo <= snr_hi", (double)p.snr_lo, (double)p.snr_hi); return QK_ERR_INVALID_ARG;
+    }
+    const size_t wave_elem = wave_dtype == QK_WAVE_I16 ? 2 : 4;
+    if (!aligned(wave, wave_elem) || !aligned(out, 4) || !aligned(lengths, 4) || (plan && !aligned(plan, 4)) || !aligned(workspace, 8) ||
+        (rirs && !aligned(rirs, 4)) || (rir_len && !aligned(rir_len, 4)) || (rir_delay && !aligned(rir_delay, 4)) ||
+        (noises && !aligned(noises, 4)) || (noise_len && !aligned(noise_len, 4)) || (counter_dev && !aligned(counter_dev, 4))) {
+        set_error("noise_reverb: pointers must be aligned to their element size (the workspace to 8 bytes)"); return QK_ERR_INVALID_ARG;
+    }
+    const int64_t limit = (int64_t)1 << 26;
+    if (max_samples < limit) {
+        const int64_t need = (int64_t)noise_reverb_workspace_bytes(batch, (int)max_samples);
+        if (workspace_bytes < need) {
+            set_error("noise_reverb: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need); return QK_ERR_INVALID_ARG;
+        }
+        const uintptr_t wa = reinterpret_cast<uintptr_t>(wave), oa = reinterpret_cast<uintptr_t>(out);
+        const size_t wave_bytes = (size_t)batch * (size_t)max_samples * wave_elem, out_bytes = (size_t)batch * (size_t)max_samples * 4;
+        if (wa < oa + out_bytes && oa < wa + wave_bytes) { set_error("noise_reverb: out overlaps wave"); return QK_ERR_INVALID_ARG; }
+    }
+    if (p.rir_stride > QK_REVERB_MAX_TAPS) {
+        set_error("noise_reverb: rir_stride %d above %d taps", p.rir_stride, QK_REVERB_MAX_TAPS); return QK_ERR_UNSUPPORTED;
+    }
+    if (max_samples >= limit) { set_error("noise_reverb: max_samples %lld must be below 2^26", (long long)max_samples); return QK_ERR_UNSUPPORTED; }
+    return check_launch(launch_noise_reverb(wave_dtype, batch, (int)max_samples, wave, lengths, p, rirs, rir_len, rir_delay, noises, noise_len,
+                                            counter_dev, out, plan, workspace, (hipStream_t)stream), "qk_noise_reverb");
+}
+
 int qk_softmax_rows_fwd(int32_t dtype, int64_t rows, int32_t cols, const float *logits, const float *bias, void *y, void *stream)
 {
     if (!logits || !y || rows < 0 || cols < 1 || cols > 64 || dtype < QK_F32 || dtype > QK_F16) { set_error("qk_softmax_rows_fwd: bad argument (1 <= cols <= 64)"); return QK_ERR_INVALID_ARG; }

@@ -388,6 +388,11 @@ int launch_spec_augment(int in_dtype, int out_dtype, int B, int P, int R, int T,
 int launch_speed_perturb(int wave_dtype, int B, int n_max, const void *wave, const int *lengths, const qk_speed_perturb_t &pol,
                          const float *tables, const unsigned *counter, int n_out, float *out, int *out_lengths, int *plan,
                          hipStream_t stream);
+// reverberation and additive noise (qk_env_aug.hip)
+size_t noise_reverb_workspace_bytes(int B, int n_max);
+int launch_noise_reverb(int wave_dtype, int B, int n_max, const void *wave, const int *lengths, const qk_noise_reverb_t &pol,
+                        const float *rirs, const int *rir_len, const int *rir_delay, const float *noises, const int *noise_len,
+                        const unsigned *counter, float *out, int *plan, void *ws, hipStream_t stream);
 int launch_relayout16(const void *src, void *dst, int n, int A, int B, hipStream_t stream);     // (n, A, B) -> (n, B, A), 16-bit
 struct PoolGeom { int batch, ih, iw, C, wh, ww, oh, ow; };
 int launch_maxpool(int dtype, bool backward, const void *x, const void *dy, void *out, const PoolGeom &g, hipStream_t stream);

@@ -116,9 +116,15 @@ def quaternion_fbank(wave, lengths=None, sample_rate=16000, winlen=0.025, winste
     wave_augment: a SpeedPerturb policy (training batches only).  The waveforms are perturbed first, and the front end runs on the
     perturbed float32 waveforms and THEIR lengths: T = num_frames of the perturbed batch's width (wider than n_max when the policy has
     a speed below 1), frame_lengths those of the perturbed utterances.  Labels are unchanged.  It combines with `augment`.  None (the
-    default): the calls are exactly those of the plain front end."""
-    if wave_augment is not None and not isinstance(wave_augment, SpeedPerturb):
-        raise TypeError('quaternion_fbank: wave_augment must be a SpeedPerturb or None, got %r' % (wave_augment,))
+    default): the calls are exactly those of the plain front end.  Also a NoiseReverb policy (reverberation and additive noise; it
+    keeps the lengths), or a tuple / list of policies applied in order -- the usual recipe is (SpeedPerturb, NoiseReverb)."""
+    if wave_augment is None or isinstance(wave_augment, (SpeedPerturb, NoiseReverb)):
+        wave_augments = () if wave_augment is None else (wave_augment,)
+    elif isinstance(wave_augment, (tuple, list)) and all(isinstance(a, (SpeedPerturb, NoiseReverb)) for a in wave_augment):
+        wave_augments = tuple(wave_augment)
+    else:
+        raise TypeError('quaternion_fbank: wave_augment must be a SpeedPerturb, a NoiseReverb, a tuple / list of them or None, got %r'
+                        % (wave_augment,))
     if augment is not None and not isinstance(augment, SpecAugment):
         raise TypeError('quaternion_fbank: augment must be a SpecAugment or None, got %r' % (augment,))
     if window not in WINDOWS:
@@ -157,8 +163,8 @@ def quaternion_fbank(wave, lengths=None, sample_rate=16000, winlen=0.025, winste
         if lengths.numel() != b:
             raise ValueError('quaternion_fbank: lengths must have B = %d entries, got %d' % (b, lengths.numel()))
         lengths = lengths.reshape(-1).to(device=wave.device, dtype=torch.int32)
-    if wave_augment is not None:
-        wave, lengths = wave_augment(wave, lengths)
+    for policy in wave_augments:
+        wave, lengths = policy(wave, lengths)
         n_max = wave.shape[1]
     bins = _mel_bins(nfilt, nfft, sample_rate, lowfreq, highfreq).astype(np.int64).tolist()
     frames = num_frames(n_max, sample_rate, winlen, winstep)
@@ -304,3 +310,119 @@ class SpeedPerturb(object):
             self._pending = counter
         else:
             self._counter.fill_(counter - (1 << 32) if counter >= 1 << 31 else counter)
+
+
+class NoiseReverb(object):
+    """A reverberation and additive-noise policy (Kaldi's wav-reverberate, Ko et al., 2017) for waveforms, with its own device
+    counter.
+
+        nr = NoiseReverb(rirs=F.prepare_rirs(synthetic_rirs(32)), noises=F.prepare_noises(synthetic_noises(8, 64000)), seed=args.seed)
+        x, il = quaternion_fbank(wave, lengths, normalize='utterance', dtype=torch.bfloat16, wave_augment=(sp, nr))   # training only
+
+    Per utterance: with probability rir_prob it is convolved with one room impulse response of the bank `rirs`
+    (functional.prepare_rirs), aligned at the response's direct path so that labels and lengths are unchanged, and with probability
+    noise_prob one recording of the bank `noises` (functional.prepare_noises) is added, from a drawn offset and wrapped around, at a
+    signal-to-noise ratio drawn from [snr[0], snr[1]) dB -- two launches (functional.noise_reverb; semantics: include/qk.h,
+    "Reverberation and additive noise").  A bank of None switches its half off.  It goes behind SpeedPerturb, as in Kaldi's recipes.
+    Nobody has measured a phone error rate with this augmentation here.
+
+    The draws are a hash of (seed, counter, utterance index): bit-repeatable from the seed.  __call__ advances the counter with a
+    device op behind the kernels, so a captured graph draws anew on every replay and nothing is read on the host (call the policy
+    once before capturing: the first call on a device creates the counter and copies the banks).
+    Data-parallel ranks must pass DIFFERENT seeds; seed and utterance index enter the hash as a sum, so keep the seeds at least a
+    batch apart (e.g. seed + 65536 * rank).
+    state_dict() / load_state_dict() carry the seed and the counter (reading the counter synchronises); the banks are not state."""
+
+    def __init__(self, rirs=None, noises=None, rir_prob=0.5, noise_prob=0.5, snr=(5.0, 20.0), seed=0):
+        rirs, noises, _ = F._env_args('NoiseReverb', rirs, noises, rir_prob, noise_prob, snr, seed)
+        self.policy = dict(rirs=rirs, noises=noises, rir_prob=float(rir_prob), noise_prob=float(noise_prob),
+                           snr=(float(snr[0]), float(snr[1])), seed=seed)
+        self._counter = None            # one int32 on the device of the first call; the kernel reads its 32 bits as unsigned
+        self._pending = 0               # counter value to start from (load_state_dict before the first call)
+        self.last_plan = None
+
+    @property
+    def seed(self):
+        return self.policy['seed']
+
+    def _counter_on(self, device):
+        if self._counter is None:
+            v = self._pending - (1 << 32) if self._pending >= 1 << 31 else self._pending
+            self._counter = torch.full((1,), v, dtype=torch.int32, device=device)
+            for name in ('rirs', 'noises'):                     # the banks move once, with the counter
+                if self.policy[name] is not None:
+                    self.policy[name] = tuple(t.to(device).contiguous() for t in self.policy[name])
+        elif self._counter.device != device:
+            raise ValueError('NoiseReverb: this policy\'s counter lives on %s, the input on %s' % (self._counter.device, device))
+        return self._counter
+
+    def __call__(self, wave, lengths):
+        """(out, lengths) with out of functional.noise_reverb for wave (B, n_max); the plan of the call is kept in .last_plan."""
+        if not torch.is_tensor(wave) or not wave.is_cuda:
+            raise RuntimeError('NoiseReverb: got a CPU tensor. Reverberation and additive noise run only on the MI355X HIP path '
+                               '(libqk_hip.so); there is no CPU fallback.')
+        counter = self._counter_on(wave.device)
+        out, self.last_plan = F.noise_reverb(wave, lengths, counter=counter, return_plan=True, **self.policy)
+        counter.add_(1)                 # wraps mod 2^32, like the kernel's key
+        return out, lengths
+
+    def state_dict(self):
+        counter = self._pending if self._counter is None else int(self._counter.item()) & 0xFFFFFFFF
+        return {'seed': self.policy['seed'], 'counter': counter}
+
+    def load_state_dict(self, d):
+        """Takes what state_dict() gave; checked on the host before anything is written."""
+        seed, counter = d['seed'], d['counter']
+        for name, v in (('seed', seed), ('counter', counter)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError('NoiseReverb.load_state_dict: %s must be an integer in [0, 2^32), got %r' % (name, v))
+        self.policy['seed'] = seed
+        if self._counter is None:
+            self._pending = counter
+        else:
+            self._counter.fill_(counter - (1 << 32) if counter >= 1 << 31 else counter)
+
+
+def synthetic_rirs(count, sample_rate=16000, rt60=(0.2, 0.8), seed=0):
+    """`count` synthetic room impulse responses (a list of float64 arrays for functional.prepare_rirs), on the host: a unit direct
+    path after 0 .. 2 ms, and behind it Gaussian noise under an exponential envelope that falls by 60 dB in a reverberation time
+    drawn from rt60 (seconds), at a drawn direct-to-reverberant level; each response is cut where its envelope has fallen by 60 dB
+    (and prepare_rirs cuts at its max_taps).  The classic Moorer / Polack model: enough to exercise and to use the augmentation
+    without a corpus of measured rooms, not a substitute for one."""
+    if isinstance(count, bool) or not isinstance(count, int) or count < 1:
+        raise ValueError('synthetic_rirs: count must be a positive integer, got %r' % (count,))
+    lo, hi = rt60
+    if not 0.0 < lo <= hi or not math.isfinite(hi) or not sample_rate > 0:
+        raise ValueError('synthetic_rirs: need 0 < rt60 low <= rt60 high and a positive sample rate')
+    rng = np.random.RandomState(seed)
+    out = []
+    for _ in range(count):
+        t60 = rng.uniform(lo, hi)
+        onset = int(rng.randint(0, max(int(0.002 * sample_rate), 1) + 1))
+        n = max(int(round(t60 * sample_rate)), 2)
+        t = np.arange(n, dtype=np.float64) / sample_rate
+        tail = rng.randn(n) * np.exp(-math.log(1000.0) * t / t60)
+        tail *= 10.0 ** (-rng.uniform(0.0, 10.0) / 20.0) / math.sqrt(float(np.sum(tail[1:] ** 2)))       # reverberant energy 0 .. -10 dB
+        tail[0] = 1.0
+        out.append(np.concatenate([np.zeros(onset), tail]))
+    return out
+
+
+def synthetic_noises(count, samples, seed=0):
+    """`count` synthetic noise recordings of `samples` samples (a list of float64 arrays for functional.prepare_noises), on the host:
+    even ones white, odd ones 1/f-shaped (pink: white noise whose spectrum is divided by sqrt(f)), each at unit power."""
+    for name, v in (('count', count), ('samples', samples)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError('synthetic_noises: %s must be a positive integer, got %r' % (name, v))
+    rng = np.random.RandomState(seed)
+    out = []
+    for i in range(count):
+        v = rng.randn(samples)
+        if i % 2 and samples > 1:
+            spec = np.fft.rfft(v)
+            spec[1:] /= np.sqrt(np.arange(1, spec.size, dtype=np.float64))
+            spec[0] = 0.0
+            v = np.fft.irfft(spec, samples)
+        power = float(np.mean(v * v))
+        out.append(v / math.sqrt(power) if power > 0 else v)
+    return out

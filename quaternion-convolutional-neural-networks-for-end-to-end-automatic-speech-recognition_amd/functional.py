@@ -1841,3 +1841,158 @@ def speed_perturb(wave, lengths, *, speeds=DEFAULT_SPEEDS, gain=(1.0, 1.0), zero
                                       _ptr(out), _ptr(out_lengths), _ptr(plan), _stream(wave))
     L.check(rc, 'qk_speed_perturb')
     return (out, out_lengths, plan) if return_plan else (out, out_lengths)
+
+
+# ---- Reverberation and additive noise (include/qk.h, "Reverberation and additive noise") ----------------------------------------
+def _bank_rows(what, name, rows, kinds):
+    """The rows of a bank as 1-D NumPy arrays, checked: a non-empty sequence of non-empty 1-D arrays of finite numbers."""
+    if isinstance(rows, (str, bytes)) or torch.is_tensor(rows) or isinstance(rows, np.ndarray):
+        raise TypeError('%s: %s must be a list of 1-D arrays, got %s' % (what, name, type(rows).__name__))
+    try:
+        rows = [np.asarray(r) for r in rows]
+    except TypeError:
+        raise TypeError('%s: %s must be a list of 1-D arrays, got %r' % (what, name, rows))
+    if not rows:
+        raise ValueError('%s: %s is empty' % (what, name))
+    for i, r in enumerate(rows):
+        if r.dtype.kind not in kinds:
+            raise TypeError('%s: %s[%d] has dtype %s' % (what, name, i, r.dtype))
+        if r.ndim != 1 or r.size < 1:
+            raise ValueError('%s: %s[%d] must be a non-empty 1-D array, got shape %s' % (what, name, i, r.shape))
+        if not np.all(np.isfinite(r)):
+            raise ValueError('%s: %s[%d] holds a value that is not finite' % (what, name, i))
+    return rows
+
+
+def prepare_rirs(rirs, max_taps=L.QK_REVERB_MAX_TAPS, device=None):
+    """A bank of room impulse responses for noise_reverb / features.NoiseReverb, built on the host in float64: every response (a 1-D
+    float array) is cut behind max_taps samples, its direct path is taken as the first argmax of |h| (the output of the
+    convolution is shifted by it, so the labels keep their places), it is scaled to unit energy and rounded once to float32; the
+    rows are padded with zeros to the longest.  Returns (rirs (R, stride) float32, rir_len (R,) int32, rir_delay (R,) int32) on
+    `device` (None: the host) -- what include/qk.h asks of the caller holds by construction."""
+    what = 'prepare_rirs'
+    if isinstance(max_taps, bool) or not isinstance(max_taps, int):
+        raise TypeError('%s: max_taps must be an integer, got %r' % (what, max_taps))
+    if not 1 <= max_taps <= L.QK_REVERB_MAX_TAPS:
+        raise ValueError('%s: max_taps %d outside 1 .. %d' % (what, max_taps, L.QK_REVERB_MAX_TAPS))
+    rows = [r.astype(np.float64)[:max_taps] for r in _bank_rows(what, 'rirs', rirs, 'f')]
+    bank = np.zeros((len(rows), max(r.size for r in rows)), dtype=np.float32)
+    delay = np.zeros(len(rows), dtype=np.int32)
+    for i, h in enumerate(rows):
+        energy = float(np.sum(h * h))
+        if not energy > 0.0:
+            raise ValueError('%s: rirs[%d] is all zeros in its first %d samples' % (what, i, max_taps))
+        delay[i] = int(np.argmax(np.abs(h)))
+        bank[i, :h.size] = (h / math.sqrt(energy)).astype(np.float32)
+    length = np.array([r.size for r in rows], dtype=np.int32)
+    return tuple(torch.from_numpy(a).to(device) if device is not None else torch.from_numpy(a) for a in (bank, length, delay))
+
+
+def prepare_noises(noises, device=None):
+    """A bank of noise recordings for noise_reverb / features.NoiseReverb: 1-D int16 or float arrays of any lengths, as float32
+    at their own scale (only the ratio of a recording's energy to the utterance's matters), rows padded with zeros to the
+    longest.  Returns (noises (N, stride) float32, noise_len (N,) int32) on `device` (None: the host)."""
+    rows = _bank_rows('prepare_noises', 'noises', noises, 'fi')
+    bank = np.zeros((len(rows), max(r.size for r in rows)), dtype=np.float32)
+    for i, v in enumerate(rows):
+        bank[i, :v.size] = v.astype(np.float32)
+    length = np.array([r.size for r in rows], dtype=np.int32)
+    return tuple(torch.from_numpy(a).to(device) if device is not None else torch.from_numpy(a) for a in (bank, length))
+
+
+def _bank_ok(what, name, bank, parts, max_stride):
+    """None, or the bank as a tuple of `parts` tensors: (rows, stride) float32 and (rows,) int32 vectors, all on one device."""
+    if bank is None:
+        return None
+    if not isinstance(bank, (tuple, list)) or len(bank) != parts or not all(torch.is_tensor(t) for t in bank):
+        raise TypeError('%s: %s must be None or the %d tensors of prepare_%s, got %r' % (what, name, parts, name, type(bank).__name__))
+    rows = bank[0]
+    if rows.dtype != torch.float32 or any(t.dtype != torch.int32 for t in bank[1:]):
+        raise TypeError('%s: %s must be a float32 matrix and int32 vectors (prepare_%s)' % (what, name, name))
+    if rows.dim() != 2 or min(rows.shape) < 1 or any(tuple(t.shape) != (rows.shape[0],) for t in bank[1:]):
+        raise ValueError('%s: %s must be a non-empty (rows, stride) matrix with one length per row' % (what, name))
+    if max_stride is not None and rows.shape[1] > max_stride:
+        raise ValueError('%s: %s rows of %d taps, more than %d' % (what, name, rows.shape[1], max_stride))
+    if any(t.device != rows.device for t in bank[1:]):
+        raise ValueError('%s: the tensors of %s live on different devices' % (what, name))
+    return tuple(bank)
+
+
+def _env_args(what, rirs, noises, rir_prob, noise_prob, snr, seed):
+    """The checked (rirs, noises, qk_noise_reverb_t); ValueError / TypeError on the host, before any device is touched."""
+    rirs = _bank_ok(what, 'rirs', rirs, 3, L.QK_REVERB_MAX_TAPS)
+    noises = _bank_ok(what, 'noises', noises, 2, None)
+    q24 = []
+    for name, v in (('rir_prob', rir_prob), ('noise_prob', noise_prob)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not 0.0 <= v <= 1.0:
+            raise ValueError('%s: %s must be a probability in [0, 1], got %r' % (what, name, v))
+        q24.append(int(round(v * (1 << 24))))
+    try:
+        lo, hi = snr
+    except (TypeError, ValueError):
+        raise ValueError('%s: snr must be a (low, high) pair in dB, got %r' % (what, snr))
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or abs(v) > 3e38:
+            raise ValueError('%s: the snr bounds must be finite numbers, got %r' % (what, snr))
+    if lo > hi:
+        raise ValueError('%s: need snr low <= snr high, got %r' % (what, snr))
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError('%s: seed must be an integer, got %r' % (what, seed))
+    if not 0 <= seed <= 0xFFFFFFFF:
+        raise ValueError('%s: seed must fit 32 unsigned bits, got %d' % (what, seed))
+    pol = L.NoiseReverbPolicy(rirs[0].shape[0] if rirs else 0, rirs[0].shape[1] if rirs else 1,
+                              noises[0].shape[0] if noises else 0, noises[0].shape[1] if noises else 1,
+                              q24[0], q24[1], float(lo), float(hi), seed)
+    return rirs, noises, pol
+
+
+def noise_reverb(wave, lengths, *, rirs=None, noises=None, rir_prob=1.0, noise_prob=1.0, snr=(5.0, 20.0), seed=0, counter=None,
+                 return_plan=False):
+    """Reverberation and additive noise for a batch of waveforms as two launches (qk_noise_reverb; semantics: include/qk.h,
+    "Reverberation and additive noise").
+
+    wave (B, n_max) int16 / float32 on the device; lengths (B,) valid samples per utterance (clamped to [0, n_max]).  rirs: a bank
+    from prepare_rirs, or None; noises: a bank from prepare_noises, or None.  Per utterance, with probability rir_prob one response
+    of the bank is drawn and the utterance convolved with it (aligned at the response's direct path, cut to the utterance's own
+    length), and with probability noise_prob one recording is drawn, started at a drawn offset, wrapped around, and added at a
+    signal-to-noise ratio drawn from [snr[0], snr[1]) dB against the (reverberated) utterance's energy.  The draws are a hash of
+    (seed, counter, utterance): equal arguments give equal bits.  counter: one-element int32 / uint32 DEVICE tensor read by the
+    kernel (None: 0).  Banks that live on another device are copied on every call: hand over device banks.
+
+    Returns out (B, n_max) float32 at the input's scale, zero from lengths[b] on; lengths do not change.  With return_plan also plan
+    (B, 8) int32 = {n, response or -1, recording or -1, offset, bits of the snr, bits of the noise gain, bits of float(signal
+    energy), bits of float(noise energy)}.  No host sync."""
+    what = 'noise_reverb'
+    rirs, noises, pol = _env_args(what, rirs, noises, rir_prob, noise_prob, snr, seed)
+    if torch.is_tensor(wave) and wave.dtype not in (torch.int16, torch.float32):
+        raise TypeError('%s: waveforms must be int16 or float32, got %s' % (what, wave.dtype))
+    if not torch.is_tensor(wave) or not wave.is_cuda:
+        raise RuntimeError('%s: got a CPU tensor. Reverberation and additive noise run only on the MI355X HIP path (libqk_hip.so); '
+                           'there is no CPU fallback.' % what)
+    if wave.dim() != 2 or min(wave.shape) < 1:
+        raise ValueError('%s: wave must be a non-empty (B, samples) tensor, got shape %s' % (what, tuple(wave.shape)))
+    b, n_max = wave.shape
+    lengths = lengths if torch.is_tensor(lengths) else torch.as_tensor(lengths)
+    if lengths.numel() != b:
+        raise ValueError('%s: lengths must have B = %d entries, got %d' % (what, b, lengths.numel()))
+    lengths = lengths.reshape(-1).to(device=wave.device, dtype=torch.int32).contiguous()
+    if counter is not None:
+        if (not torch.is_tensor(counter) or counter.device != wave.device or counter.numel() != 1
+                or counter.dtype not in (torch.int32, torch.uint32)):
+            raise ValueError('%s: counter must be a one-element int32 / uint32 tensor on %s' % (what, wave.device))
+    if n_max >= 1 << 26:
+        raise ValueError('%s: rows of %d samples are not supported (limit 2^26)' % (what, n_max))
+    rirs = tuple(t.to(wave.device).contiguous() for t in rirs) if rirs else (None, None, None)
+    noises = tuple(t.to(wave.device).contiguous() for t in noises) if noises else (None, None)
+    wave = wave.contiguous()
+    out = torch.empty((b, n_max), dtype=torch.float32, device=wave.device)
+    plan = torch.empty((b, L.QK_NOISE_REVERB_PLAN_WORDS), dtype=torch.int32, device=wave.device) if return_plan else None
+    n = int(L.lib().qk_noise_reverb_workspace_bytes(b, n_max))
+    ws = torch.empty(n // 8, dtype=torch.float64, device=wave.device)
+    wd = L.QK_WAVE_I16 if wave.dtype == torch.int16 else L.QK_WAVE_F32
+    with _on_device(wave.device):
+        rc = L.lib().qk_noise_reverb(wd, b, n_max, _ptr(wave), _ptr(lengths), ctypes.byref(pol), _ptr(rirs[0]), _ptr(rirs[1]),
+                                     _ptr(rirs[2]), _ptr(noises[0]), _ptr(noises[1]), _ptr(counter), _ptr(out), _ptr(plan), _ptr(ws), n,
+                                     _stream(wave))
+    L.check(rc, 'qk_noise_reverb')
+    return (out, plan) if return_plan else out
