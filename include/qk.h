@@ -161,7 +161,8 @@ const char *qk_last_error(void);
 #define QK_DBG_NO_FUSED_FIRST 0x1000000u   /* first layer + frequency pooling as conv, activation and pooling passes instead of qk_conv_*_pool_* */
 #define QK_DBG_NO_DENSE_IN_CHAIN 0x2000000u /* the TimeDistributed quaternion-dense layers outside the backward chain */
 #define QK_DBG_NO_FUSED_SOFTMAX 0x4000000u /* Dense(62, softmax) through torch ops instead of the fused output-layer kernels */
-#define QK_DBG_BAND16_8WAVES 16u   /* 16-bit band kernels: 8-wave workgroups (one per CU) instead of 4-wave (two per CU) */
+#define QK_DBG_NO_MASK_BITS 0x8000000u     /* relu + Dropout chains re-read y as the backward-data mask instead of its bit-packed form (qk_conv_*_post_bits; env QK_NO_MASK_BITS) */
+#define QK_DBG_BAND16_8WAVES 16u  /* 16-bit band kernels: 8-wave workgroups (one per CU) instead of 4-wave (two per CU) */
 unsigned qk_set_debug_flags(unsigned flags);
 /* Profiling only: a device buffer (64 bytes per workgroup, 65536 workgroups) into which the 16-bit band kernels drop shader-clock time stamps of their
  * phases (start, prologue done, K loop done, end) and the CU they ran on -- probe builds only (tools/probe/build_variant.sh); NULL switches it off. */
@@ -299,6 +300,35 @@ int qk_conv_fwd_post(const qk_conv_desc_t *desc, const qk_postop_t *post, const 
 int qk_conv_bwd_post(const qk_conv_desc_t *desc, const void *x, const void *dy, const float *w, void *dx, float *dw,
                      float *dbias, const qk_postop_t *post_x, const void *x_pre, float *dalpha_x, int32_t flags,
                      void *workspace, size_t workspace_bytes, void *stream);
+
+/* Bit-packed mask of the relu form.  In a run of layers y_L = drop(relu(pre_L)) the backward-data epilogue of layer L+1
+ * reads y_L again only to learn `y > 0`: 16 bits per element for one.  The _bits entry points move that predicate to
+ * the producer: the forward epilogue that stores y also stores ONE BIT per element, and the next layer's backward-data
+ * reads the bits instead of y (y itself is still written and still the backward-weight operand).
+ *
+ * Layout (one for every producer and consumer): bit i belongs to element i of y in its channels_last buffer -- byte
+ * i >> 3, bit i & 7; a row of 4 fq elements is fq / 2 bytes, 8 consecutive elements are one byte.  The buffer is the
+ * caller's, 16-byte aligned, qk_conv_mask_bits_bytes(desc) bytes (ceil(elements / 8) rounded up to 16), separate from
+ * the workspace.  The bit is exactly the predicate qk_conv_bwd_post evaluates on y: `y > 0` on the value widened to
+ * float -- clear for NaN and -0, set for subnormals and +inf -- so both roads give the same dx bit for bit.
+ *
+ * qk_conv_mask_bits_bytes: size of the bit tensor of THIS layer's output, or 0 when no forward kernel of this layer
+ *   writes bits (then qk_conv_fwd_post_bits returns QK_ERR_UNSUPPORTED).  Writers: the 16-bit band kernels, channel
+ *   counts that are multiples of 32, channels_last, unit stride and dilation.
+ * qk_conv_bwd_reads_mask_bits: 1 when this layer's backward-data can read the bits of its INPUT x (16-bit band and
+ *   point kernels, multiples of 32), else 0 (then qk_conv_bwd_post_bits returns QK_ERR_UNSUPPORTED).
+ * Both follow the diagnostic switches in force when they are called; neither launches anything.
+ * qk_conv_fwd_post_bits: qk_conv_fwd_post for the relu form (post->alpha == NULL), which also writes mask_bits.
+ * qk_conv_bwd_post_bits: qk_conv_bwd_post for the relu form with x_mask_bits (the bits of x) in place of reading x as
+ *   the mask; x is read by backward-weight only. */
+size_t qk_conv_mask_bits_bytes(const qk_conv_desc_t *desc);
+int qk_conv_bwd_reads_mask_bits(const qk_conv_desc_t *desc);
+int qk_conv_fwd_post_bits(const qk_conv_desc_t *desc, const qk_postop_t *post, const void *x, const float *w,
+                          const float *bias, void *pre, void *y, void *mask_bits, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int qk_conv_bwd_post_bits(const qk_conv_desc_t *desc, const void *x, const void *x_mask_bits, const void *dy,
+                          const float *w, void *dx, float *dw, float *dbias, const qk_postop_t *post_x, int32_t flags,
+                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* The post-op on its own (any dtype / shape, HBM-bound): `t` describes the channels_last activation
  * (batch, spatial[0..rank-1], channels) -- only batch, rank, out_spatial, fq (channels = 4 * fq) and dtype of a

@@ -26,6 +26,7 @@ QK_DBG_NO_SMALL16 = 0x40000
 # graph-level A/B switches (include/qk.h): kept in the library's mask, acted on by models/interspeech_model.py and layers.py
 QK_DBG_NO_CONV_CHAIN, QK_DBG_NO_FUSED_PRELU, QK_DBG_NO_FUSED_DROPOUT, QK_DBG_NO_FUSED_CTC = 0x100000, 0x200000, 0x400000, 0x800000
 QK_DBG_NO_FUSED_FIRST, QK_DBG_NO_DENSE_IN_CHAIN, QK_DBG_NO_FUSED_SOFTMAX = 0x1000000, 0x2000000, 0x4000000
+QK_DBG_NO_MASK_BITS = 0x8000000        # relu + dropout chains: the next layer's backward-data re-reads y instead of its bit-packed mask (functional._ConvChainFn)
 QK_WAVE_F32, QK_WAVE_I16 = 0, 1                                  # acoustic front end (qk_fbank_quaternion)
 QK_WINDOW_RECT, QK_WINDOW_HAMMING = 0, 1
 QK_FBANK_NORM_NONE, QK_FBANK_NORM_UTTERANCE = 0, 1
@@ -124,6 +125,10 @@ SYMBOLS = {
     'qk_conv_bwd_data': (ctypes.c_int, [_CD, _VP, _VP, _FP, _VP, _VP, _SZ, _VP]),
     'qk_conv_fwd_post': (ctypes.c_int, [_CD, _PO, _VP, _FP, _FP, _VP, _VP, _VP, _SZ, _VP]),
     'qk_conv_bwd_post': (ctypes.c_int, [_CD, _VP, _VP, _FP, _VP, _FP, _FP, _PO, _VP, _FP, I32, _VP, _SZ, _VP]),
+    'qk_conv_mask_bits_bytes': (_SZ, [_CD]),
+    'qk_conv_bwd_reads_mask_bits': (ctypes.c_int, [_CD]),
+    'qk_conv_fwd_post_bits': (ctypes.c_int, [_CD, _PO, _VP, _FP, _FP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    'qk_conv_bwd_post_bits': (ctypes.c_int, [_CD, _VP, _VP, _VP, _FP, _VP, _FP, _FP, _PO, I32, _VP, _SZ, _VP]),
     'qk_postop_fwd': (ctypes.c_int, [_CD, _PO, _VP, _VP, _VP]),
     'qk_postop_bwd': (ctypes.c_int, [_CD, _PO, _VP, _VP, _VP, _FP, _VP]),
     'qk_conv_bwd_weight': (ctypes.c_int, [_CD, _VP, _VP, _VP, _FP, _FP, _VP, _SZ, _VP]),

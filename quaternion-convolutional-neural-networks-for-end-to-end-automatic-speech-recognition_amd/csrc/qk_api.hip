@@ -41,6 +41,7 @@ unsigned env_flags()
     if (getenv("QK_NO_FUSED_FIRST")) f |= QK_DBG_NO_FUSED_FIRST;
     if (getenv("QK_NO_DENSE_IN_CHAIN")) f |= QK_DBG_NO_DENSE_IN_CHAIN;
     if (getenv("QK_NO_FUSED_SOFTMAX")) f |= QK_DBG_NO_FUSED_SOFTMAX;
+    if (getenv("QK_NO_MASK_BITS")) f |= QK_DBG_NO_MASK_BITS;
     if (const char *ab = getenv("QK_ABLATE")) f |= ((unsigned)atoi(ab) << kDbgAblateShift) & kDbgAblateMask;
     return f;
 }
@@ -139,6 +140,9 @@ QK_DECL(f16)
 int try_hgemm_16(int dtype, const void *in, const void *mask, const float *w_f32, const float *bias,
                  void *out, const GemmGeom &g, bool w_is_transposed, void *ws, size_t ws_bytes,
                  hipStream_t stream);
+
+// kernel a call carrying a bit-packed kind-2 mask would reach: 2 = band, 1 = point, 0 = none (qk_hgemm_bf16mfma.hip)
+int hgemm16_bits_route(int dtype, const GemmGeom &g);
 
 // 16-bit-input MFMA backward-weight, band form (qk_wgrad_band_bf16mfma.hip); returns 1 when it took the call
 int try_wgrad_band_16(int dtype, const void *x, const void *dy, const void *ymask, float *dw, float *dbias,
@@ -419,12 +423,34 @@ CfPlan cf_plan(const qk_conv_desc_t *d, int op)
 
 size_t ws_bytes_impl(const qk_conv_desc_t *d, int op) { return cf16_ok(d) ? cf_plan(d, op).total : kernel_ws(d, op).total; }
 
+// the forward call of qk_conv_fwd_post(_bits) as the 16-bit dispatcher sees it (call-specific fields of the geometry)
+bool fwd_post_geom(const qk_conv_desc_t *d, const PostOp &post, const void *pre, const void *y, GemmGeom *g)
+{
+    *g = make_geom(d, false);
+    g->relu = d->activation == QK_ACT_RELU;
+    g->has_bias = d->has_bias ? 1 : 0;
+    if (d->dtype == QK_F32 || !post.kind || d->layout != QK_CH_LAST || !aligned(pre, 16) || !aligned(y, 16) ||
+        (long long)g->M * 4 * d->fq >= (1ll << 32)) return false;         // the dropout hash indexes elements with 32 bits
+    g->post = post; g->post_fwd = 1; g->pre_out = post.kind == 1 ? const_cast<void *>(pre) : nullptr;
+    return true;
+}
+
 int conv_fwd_impl(const qk_conv_desc_t *d, const void *x, const float *w, const float *bias, void *y,
-                  void *ws, size_t wsb, hipStream_t stream, const PostOp *post = nullptr, void *pre = nullptr)
+                  void *ws, size_t wsb, hipStream_t stream, const PostOp *post = nullptr, void *pre = nullptr,
+                  void *mask_bits = nullptr)
 {
     if (!x || !w || !y) { set_error("x/w/y must not be NULL"); return QK_ERR_INVALID_ARG; }
     if (d->has_bias && !bias) { set_error("has_bias set but bias is NULL"); return QK_ERR_INVALID_ARG; }
     ProfScope prof_scope(QK_OP_FWD, d, stream);
+    if (mask_bits) {
+        // the bit-packed mask is written by ONE kernel family's epilogue: that kernel or an error
+        GemmGeom g;
+        if (cf16_ok(d) || !post || post->kind != 2 || !fwd_post_geom(d, *post, pre, y, &g)) { set_error("mask bits: relu-form post-op on 16-bit channels_last tensors only"); return QK_ERR_UNSUPPORTED; }
+        g.bits_out = mask_bits;
+        const int r = try_hgemm_16(d->dtype, x, nullptr, w, bias, y, g, false, ws, wsb, stream);
+        if (r == 0 || r == QK_ERR_UNSUPPORTED) { set_error("mask bits: no forward kernel writes them for this layer (qk_conv_mask_bits_bytes)"); return QK_ERR_UNSUPPORTED; }
+        return r < 0 ? r : 0;
+    }
     if (cf16_ok(d)) {
         const qk_conv_desc_t c = as_ch_last(d);
         const CfPlan p = cf_plan(d, QK_OP_FWD);
@@ -465,7 +491,7 @@ int conv_fwd_impl(const qk_conv_desc_t *d, const void *x, const float *w, const 
 
 int conv_bwd_data_impl(const qk_conv_desc_t *d, const void *dy, const void *y, const float *w, void *dx,
                        void *ws, size_t wsb, hipStream_t stream, const void *dx_mask = nullptr,
-                       const PostOp *post = nullptr, float *dalpha = nullptr)
+                       const PostOp *post = nullptr, float *dalpha = nullptr, const void *dx_mask_bits = nullptr)
 {
     // post != NULL: dx_mask holds the PRE-activation of x (x = post(x_pre); kind 2: x itself); dx returns d loss / d x_pre
     const bool with_post = post && post->kind;
@@ -479,6 +505,17 @@ int conv_bwd_data_impl(const qk_conv_desc_t *d, const void *dy, const void *y, c
     }
     if (need && !aligned(ws, 16)) { set_error("workspace must be 16-byte aligned"); return QK_ERR_WORKSPACE; }
     ProfScope prof_scope(QK_OP_BWD_DATA, d, stream);
+    if (dx_mask_bits) {
+        // (bit-packed kind-2 mask of x in place of dx_mask: the band / point kernels' epilogue or an error)
+        if (cf16_ok(d) || mask || !with_post || post->kind != 2 || d->dtype == QK_F32 || d->layout != QK_CH_LAST || !aligned(dx_mask_bits, 16)) {
+            set_error("mask bits: relu-form post-op on 16-bit channels_last tensors, 16-byte aligned bits"); return QK_ERR_UNSUPPORTED;
+        }
+        GemmGeom g = make_geom(d, true);
+        g.post = *post; g.ep_bits = dx_mask_bits;
+        const int r = try_hgemm_16(d->dtype, dy, nullptr, w, nullptr, dx, g, true, ws, wsb, stream);
+        if (r == 0 || r == QK_ERR_UNSUPPORTED) { set_error("mask bits: no backward-data kernel reads them for this layer (qk_conv_bwd_reads_mask_bits)"); return QK_ERR_UNSUPPORTED; }
+        return r < 0 ? r : 0;
+    }
     if (cf16_ok(d)) {
         // (`need` above is this plan's total: every slot fits)
         const qk_conv_desc_t c = as_ch_last(d);
@@ -763,6 +800,60 @@ int qk_conv_bwd_post(const qk_conv_desc_t *desc, const void *x, const void *dy, 
     // relu post-op: x = drop(relu(x_pre)) is its own mask (x > 0 <=> x_pre > 0 and kept)
     const void *mask_src = p.kind == 2 ? x : x_pre;
     return check_launch(conv_bwd_data_impl(desc, dy, nullptr, w, dx, workspace, bd, (hipStream_t)stream, mask_src, &p, p.kind == 2 ? nullptr : dalpha_x), "qk_conv_bwd_post");
+}
+
+size_t qk_conv_mask_bits_bytes(const qk_conv_desc_t *desc)
+{
+    if (validate(desc, false) || cf16_ok(desc) || desc->activation != QK_ACT_LINEAR) return 0;
+    PostOp p;
+    memset(&p, 0, sizeof(p));
+    p.kind = 2; p.alpha_sel = -1; p.drop_scale = 1.f;
+    GemmGeom g;
+    if (!fwd_post_geom(desc, p, nullptr, nullptr, &g)) return 0;
+    g.bits_out = &g;                                                    // (any non-NULL value: the route asks only whether it is set)
+    if (hgemm16_bits_route(desc->dtype, g) != 2) return 0;
+    const size_t bytes = ((size_t)g.M * 4 * desc->fq + 7) / 8;
+    return (bytes + 15) / 16 * 16;
+}
+
+int qk_conv_bwd_reads_mask_bits(const qk_conv_desc_t *desc)
+{
+    if (validate(desc, false) || cf16_ok(desc) || desc->activation != QK_ACT_LINEAR || desc->dtype == QK_F32 || desc->layout != QK_CH_LAST) return 0;
+    GemmGeom g = make_geom(desc, true);
+    g.post.kind = 2; g.post.alpha_sel = -1; g.post.drop_scale = 1.f;
+    g.ep_bits = &g;
+    return hgemm16_bits_route(desc->dtype, g) != 0 ? 1 : 0;
+}
+
+int qk_conv_fwd_post_bits(const qk_conv_desc_t *desc, const qk_postop_t *post, const void *x, const float *w,
+                          const float *bias, void *pre, void *y, void *mask_bits, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (int rc = validate(desc, false)) return rc;
+    if (!post || !mask_bits || !aligned(mask_bits, 16)) { set_error("qk_conv_fwd_post_bits: post / mask_bits must not be NULL, mask_bits 16-byte aligned"); return QK_ERR_INVALID_ARG; }
+    if (post->alpha) { set_error("qk_conv_fwd_post_bits: the relu form only (alpha == NULL)"); return QK_ERR_UNSUPPORTED; }
+    if (desc->activation != QK_ACT_LINEAR) { set_error("qk_conv_fwd_post_bits: the convolution must be LINEAR (the post-op is the activation)"); return QK_ERR_INVALID_ARG; }
+    PostOp p;
+    if (int rc = to_postop(post, desc->rank, desc->out_spatial, &p)) return rc;
+    return check_launch(conv_fwd_impl(desc, x, w, bias, y, workspace, workspace_bytes, (hipStream_t)stream, &p, pre, mask_bits), "qk_conv_fwd_post_bits");
+}
+
+int qk_conv_bwd_post_bits(const qk_conv_desc_t *desc, const void *x, const void *x_mask_bits, const void *dy, const float *w, void *dx,
+                          float *dw, float *dbias, const qk_postop_t *post_x, int32_t flags, void *workspace, size_t workspace_bytes,
+                          void *stream)
+{
+    if (int rc = validate(desc, false)) return rc;
+    if (!dx || !post_x || !x_mask_bits) { set_error("qk_conv_bwd_post_bits: dx / post_x / x_mask_bits must not be NULL"); return QK_ERR_INVALID_ARG; }
+    if (post_x->alpha) { set_error("qk_conv_bwd_post_bits: the relu form only (alpha == NULL)"); return QK_ERR_UNSUPPORTED; }
+    if (flags & ~QK_BWD_ACCUMULATE) { set_error("qk_conv_bwd_post_bits: only QK_BWD_ACCUMULATE is a valid flag here (0x%x)", flags); return QK_ERR_INVALID_ARG; }
+    if (desc->activation != QK_ACT_LINEAR) { set_error("qk_conv_bwd_post_bits: the layer must be LINEAR"); return QK_ERR_INVALID_ARG; }
+    if (!qk_conv_bwd_reads_mask_bits(desc)) { set_error("qk_conv_bwd_post_bits: no backward-data kernel reads mask bits for this layer"); return QK_ERR_UNSUPPORTED; }
+    PostOp p;
+    if (int rc = to_postop(post_x, desc->rank, desc->in_spatial, &p)) return rc;
+    const size_t bd = ws_bytes_impl(desc, QK_OP_BWD_DATA);
+    if (bd && (!workspace || workspace_bytes < bd)) { set_error("bwd needs %zu workspace bytes, got %zu", bd, workspace_bytes); return QK_ERR_WORKSPACE; }
+    if (int rc = conv_bwd_weight_impl(desc, x, dy, nullptr, dw, dbias, nullptr, (hipStream_t)stream, (flags & QK_BWD_ACCUMULATE) != 0,
+                                      workspace, workspace_bytes)) return check_launch(rc, "qk_conv_bwd_post_bits");
+    return check_launch(conv_bwd_data_impl(desc, dy, nullptr, w, dx, workspace, bd, (hipStream_t)stream, nullptr, &p, nullptr, x_mask_bits), "qk_conv_bwd_post_bits");
 }
 
 static int postop_entry(const qk_conv_desc_t *t, const qk_postop_t *post, bool backward, const void *pre, const void *dy,

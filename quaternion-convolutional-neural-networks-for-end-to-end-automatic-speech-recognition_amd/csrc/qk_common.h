@@ -82,6 +82,12 @@ struct GemmGeom {
     int post_fwd;                        // the post-op is applied to THIS kernel's output (forward); else (ep_mask set) its derivative
     void *pre_out;                       // forward, kind 1: where the pre-activation goes (kind 2 writes y only)
     float *dalpha;
+    // bit-packed kind-2 mask (qk_postop.h): bit i = (element i of the channels-last tensor > 0), byte i >> 3, bit i & 7.
+    // bits_out: the forward relu-form epilogue also writes the bits of its y (band kernels, unpadded forms);
+    // ep_bits: backward-data reads them IN PLACE OF ep_mask (band and point kernels).  A shape that reaches a kernel
+    // without the matching epilogue is QK_ERR_UNSUPPORTED, never a silent detour.
+    void *bits_out;
+    const void *ep_bits;
     int b_wp, b_nlines, b_cshift, b_rev;
     // k_hgemm16 row order: 0 = rows run over (n, o0, o1, o2); batch = rows run over (o0, n, o1, o2) (dv_*[2] then divides
     // by batch).  Chosen when the gathered tensor has ONE position along axis 0 under a multi-tap kernel axis (the

@@ -584,7 +584,8 @@ constexpr int band_op(int R, int K, int ti, int k)
 //     (g.Qp, g.Jp), band units of channels >= Q are out-of-range DMA lanes (zeros), output pieces of channels >= J are not
 //     stored.  The matrix cores then run 2x (one side padded) to 4x the algorithmic MFMAs -- still several times the fp32-MFMA
 //     path these shapes took before; the unpadded instantiations are untouched.
-template <typename T, int WM, int WN, int KIN, bool CONJ, bool TRIM, bool EPM, bool POSTF, bool PAD = false>
+// EPM: 0 = no epilogue mask, 1 = the 16-bit tensor g.ep_mask, 2 = its bit-packed form g.ep_bits (relu post-op only, unpadded forms)
+template <typename T, int WM, int WN, int KIN, bool CONJ, bool TRIM, int EPM, bool POSTF, bool PAD = false>
 __global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_hgemm16_band(const T *__restrict__ in, const uint4 *__restrict__ wq, const T *__restrict__ zero_line,
                const float *__restrict__ bias, T *__restrict__ out, const GemmGeom g)
@@ -790,6 +791,30 @@ k_hgemm16_band(const T *__restrict__ in, const uint4 *__restrict__ wq, const T *
 
     const int frow = wm * 32 + lr;                  // tile row this lane reads; band row = frow + tap offset
     const int b_rd0 = wn * 32 + lr;
+
+    // Where the bit-packed epilogue mask (EPM == 2) is fetched.  Default: at the epilogue head.  -DQK_BITS_PROLOGUE=1 (an A/B build,
+    // tools/probe/build_variant.sh) fetches it here, a whole K loop ahead of its use: four more VGPRs live across a loop that sits at
+    // 256 in the 5-tap forms (profiles/mask_bits_ab.txt).
+#ifndef QK_BITS_PROLOGUE
+#define QK_BITS_PROLOGUE 0
+#endif
+    uint4 ebv = make_uint4(0u, 0u, 0u, 0u);       // (one dword per component; a vector, not an array: see the note on captured arrays in k_hgemm16)
+    auto load_ep_bits = [&]() {
+        // the lane pair (lr, lh = 0 / 1) of a row shares ONE dword per component -- the bits of channels j0 + wn 32 .. + 31, at byte
+        // (row 4 J + b J + j0 + wn 32) / 8 -- and piece q of half lh is its byte 2 q + lh: 4 VGPRs in place of the 32 of em[][], 16 bytes
+        // per row in place of 256 (J = 32: the row's 16 bytes are one load)
+        const int tr_ = wm * 32 + lr, P = p0 + tr_;
+        const int line = fastdiv(P, g.dv_mul[0], g.dv_shr[0]), u = P - line * WP;
+        if (!(line < g.b_nlines && u < g.osp[2] && (!TRIM || tr_ < BMU))) return;
+        const unsigned char *bp = static_cast<const unsigned char *>(g.ep_bits) + (((long long)(line * g.osp[2] + u) * (int)g.out_ss + j0 + wn * 32) >> 3);
+        if (g.J == 32) ebv = *reinterpret_cast<const uint4 *>(bp);
+        else {
+            const int cb = g.J >> 3;                  // bytes of one component's bits in a row
+            ebv = make_uint4(*reinterpret_cast<const unsigned *>(bp), *reinterpret_cast<const unsigned *>(bp + cb),
+                             *reinterpret_cast<const unsigned *>(bp + 2 * cb), *reinterpret_cast<const unsigned *>(bp + 3 * cb));
+        }
+    };
+    if constexpr (EPM == 2 && QK_BITS_PROLOGUE) load_ep_bits();
 
     // ---- prologue: band 0 in LDS, B tile 0 on its way there (its DMA leads, the band's loads are behind it: their stores wait for both)
     b_prep();                                        // (the B tile needs no row decode: its loads lead)
@@ -1003,7 +1028,7 @@ k_hgemm16_band(const T *__restrict__ in, const uint4 *__restrict__ wq, const T *
     QK_STAMP(2);
     if ((g.ablate & 8) && acc[0][0] != 123.456f) return;              // (ablate 8: profiling, no epilogue)
     const bool post_on = (EPM || POSTF) && g.post.kind != 0;
-    const PostOp psd = (EPM || POSTF) ? resolve_seed(g.post) : g.post;
+    const PostOp psd = (EPM == 1 || POSTF) ? resolve_seed(g.post) : g.post;      // (the bit form never hashes: no seed to resolve)
     const int tr = wm * 32 + lr;                                     // row inside the tile
     bool o_ok;
     long long o_row;                                                 // element offset of the lane's first piece, component 0
@@ -1026,8 +1051,8 @@ k_hgemm16_band(const T *__restrict__ in, const uint4 *__restrict__ wq, const T *
     // (the K loop's last barrier is behind every wave: the tile buffers are free)
     if (EPM && post_on && g.dalpha && tid < 256) aslab[tid] = 0.f;
     if (EPM && post_on && g.dalpha) __syncthreads();
-    uint4 em[EPM ? 4 : 1][2];
-    if (EPM && g.ep_mask) {
+    uint4 em[EPM == 1 ? 4 : 1][2];
+    if (EPM == 1 && g.ep_mask) {
 #pragma unroll
         for (int b = 0; b < 4; ++b)
 #pragma unroll
@@ -1036,6 +1061,11 @@ k_hgemm16_band(const T *__restrict__ in, const uint4 *__restrict__ wq, const T *
                                ? *reinterpret_cast<const uint4 *>(static_cast<const T *>(g.ep_mask) + o_row + b * g.J + q * 16)
                                : make_uint4(0u, 0u, 0u, 0u);
     }
+    if constexpr (EPM == 2 && !QK_BITS_PROLOGUE) load_ep_bits();      // (bit-packed mask, qk_postop.h: see the prologue)
+    const unsigned eb[4] = {ebv.x, ebv.y, ebv.z, ebv.w};
+    const long long bit_row = (o_row - lh * 8) >> 3;                 // producer: byte of component 0's dword of this row's bits
+    const bool want_bits = POSTF && !PAD && NW == 4 && post_on && g.bits_out != nullptr;
+    unsigned ob[4] = {0u, 0u, 0u, 0u};                                // producer: this lane's two bytes of each component's dword
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
         unsigned pk[4][2];
@@ -1058,19 +1088,40 @@ k_hgemm16_band(const T *__restrict__ in, const uint4 *__restrict__ wq, const T *
             uint4 v = make_uint4(s0[0], s1[0], s0[1], s1[1]);
             if (o_ok && (!PAD || j0 + wn * 32 + q * 16 + lh * 8 < g.J)) {       // (PAD: a 16-byte piece lies inside or outside J as a whole)
                 const long long o = o_row + b * g.J + q * 16;
-                if constexpr (EPM) {
+                if constexpr (EPM == 1) {
                     if (g.ep_mask) {
                         if (post_on) v = post_bwd8<T>(v, em[b][q], a_val, (unsigned)o, psd, dal);
                         else v = mask8(v, em[b][q]);
                     }
                 }
+                if constexpr (EPM == 2) v = post_bwd8_relu_bits<T>(v, (eb[b] >> (q * 16 + lh * 8)) & 0xffu, psd.drop_scale);
                 if constexpr (POSTF) {
                     if (post_on) {
                         if (g.pre_out) *reinterpret_cast<uint4 *>(static_cast<T *>(g.pre_out) + o) = v;
                         v = post_fwd8<T>(v, a_val, (unsigned)o, psd);
+                        // (the bits of the PACKED values about to be stored: what a consumer reading y would see)
+                        if (want_bits) ob[b] |= gt0_bits8<T>(v) << (q * 16 + lh * 8);
                     }
                 }
                 *reinterpret_cast<uint4 *>(out + o) = v;
+            }
+        }
+    }
+    if constexpr (POSTF && !PAD && NW == 4) {
+        if (want_bits) {
+            // One owner lane per byte, plain vector stores: a v_permlane32_swap ORs the lh halves of two components' dwords at once
+            // (lanes 0..31 end up with components 0 and 2, lanes 32..63 with 1 and 3 of their row); rows that store no y store no bits.
+            const auto s01 = __builtin_amdgcn_permlane32_swap(ob[0], ob[1], false, false);
+            const auto s23 = __builtin_amdgcn_permlane32_swap(ob[2], ob[3], false, false);
+            const unsigned d_lo = s01[0] | s01[1], d_hi = s23[0] | s23[1];          // component lh, component 2 + lh
+            unsigned char *bp = static_cast<unsigned char *>(g.bits_out) + bit_row;
+            if (g.J == 32) {
+                // the row's 16 bytes: one more swap leaves components (0, 1) in lanes 0..31 and (2, 3) in lanes 32..63 -- 8-byte stores
+                const auto sw = __builtin_amdgcn_permlane32_swap(d_lo, d_hi, false, false);
+                if (o_ok) *reinterpret_cast<uint2 *>(bp + lh * 8) = make_uint2(sw[0], sw[1]);
+            } else if (o_ok) {
+                *reinterpret_cast<unsigned *>(bp + lh * (g.J >> 3)) = d_lo;
+                *reinterpret_cast<unsigned *>(bp + (2 + lh) * (g.J >> 3)) = d_hi;
             }
         }
     }
@@ -1108,7 +1159,7 @@ k_hgemm16_band(const T *__restrict__ in, const uint4 *__restrict__ wq, const T *
 // ---------------------------------------------------------------------------------------
 // WN = 1 (round 5, late): 32-channel column blocks, 256-row tiles -- produced widths that are multiples of 32 but not of 64 (the head's
 // backward-data of a start_filter = 16 model: 64 -> 32) ran the general implicit-GEMM kernel at 6 % of peak (0.28 ms for 184 MB).
-template <typename T, int NKC, bool EPM, int WN = 2>
+template <typename T, int NKC, int EPM, int WN = 2>      // EPM: 0 / 1 (g.ep_mask) / 2 (g.ep_bits, relu post-op), as k_hgemm16_band
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_hgemm16_point(const T *__restrict__ in, const uint4 *__restrict__ wq, const float *__restrict__ bias,
                 T *__restrict__ out, const GemmGeom g, const int n_tiles, const int n_units, const unsigned in_bytes,
@@ -1168,7 +1219,7 @@ k_hgemm16_point(const T *__restrict__ in, const uint4 *__restrict__ wq, const fl
     // Stores and mask loads go through buffer resources, rows past the end get an out-of-range offset: no branch
     // around them.
     const __amdgpu_buffer_rsrc_t rout = make_rsrc16(out, out_bytes);
-    const __amdgpu_buffer_rsrc_t rmask = make_rsrc16(EPM ? g.ep_mask : out, out_bytes);
+    const __amdgpu_buffer_rsrc_t rmask = EPM == 2 ? make_rsrc16(g.ep_bits, out_bytes / 16u) : make_rsrc16(EPM ? g.ep_mask : out, out_bytes);
 
     for (int u = u_lo; u < u_hi; ++u) {
         const int slice = u / n_tiles, tile = u - slice * n_tiles;      // slice = tap * JB + jb
@@ -1211,12 +1262,22 @@ k_hgemm16_point(const T *__restrict__ in, const uint4 *__restrict__ wq, const fl
         const int ntile = (u + 1) % n_tiles;
         const unsigned vnext = more ? row_voff(ntile * BM + wm * 32 + lr) : kOutOfRange16;
 
-        uint4 em[EPM ? 4 : 1][2];
-        if constexpr (EPM) {
+        uint4 em[EPM == 1 ? 4 : 1][2];
+        unsigned eb[4] = {0u, 0u, 0u, 0u};
+        if constexpr (EPM == 1) {
 #pragma unroll
             for (int b = 0; b < 4; ++b)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) em[b][q] = buf_load16b(rmask, (g.ablate & 16) ? kOutOfRange16 : o_off, (unsigned)(b * g.J + q * 16) * 2u);
+        }
+        if constexpr (EPM == 2) {
+            // bit form: ONE dword per component and lane pair (the bits of the wave's 32 channels; byte 2 q + lh is piece q of this
+            // half), at byte (element index) / 8 of the bit tensor -- o_off / 16 is that byte for this lane's first piece; rows past
+            // the end keep the out-of-range offset and read zeros
+            const unsigned boff = (o_off == kOutOfRange16 || (g.ablate & 16)) ? kOutOfRange16 : (o_off >> 4) - (unsigned)lh;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                eb[b] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rmask, (int)boff, (int)((unsigned)(b * g.J) >> 3), 0);
         }
         floatx16 acc[4], accn[4];
 #pragma unroll
@@ -1276,8 +1337,11 @@ k_hgemm16_point(const T *__restrict__ in, const uint4 *__restrict__ wq, const fl
                 const auto s1 = __builtin_amdgcn_permlane32_swap(pk[2 * q][1], pk[2 * q + 1][1], false, false);
                 uint4 v = make_uint4(s0[0], s1[0], s0[1], s1[1]);
                 const unsigned soff = (unsigned)(b * g.J + q * 16) * 2u;
-                if constexpr (EPM) {
-                    if (relu_bwd) v = mask8(v, em[b][q]);
+                if constexpr (EPM == 2) v = keep_bits8(v, (eb[b] >> (q * 16 + lh * 8)) & 0xffu);
+                else if constexpr (EPM == 1) {
+                    // (relu form: the predicate of post_bwd8_relu, y > 0.f -- one definition for the 16-bit mask and its bit form;
+                    //  mask8's integer test differed from it for a positive NaN in y, which relu never produces)
+                    if (relu_bwd) v = keep_bits8(v, gt0_bits8<T>(em[b][q]));
                     else if (post_on) v = post_bwd8<T>(v, em[b][q], a_val, (o_off + soff) / 2u, psd, dal);
                     else v = mask8(v, em[b][q]);
                 } else {
@@ -1303,8 +1367,9 @@ inline bool point_geom(const GemmGeom &g, GemmGeom *o)
     if (g.post.kind != 0) {
         // the backward form (derivative in the epilogue, pre-activation / y in ep_mask), or -- round 4 -- the forward RELU form
         // y = dropout(relu(pre)) with its single output tensor (the TimeDistributed dense layers of the TIMIT model as chain links)
-        const bool fwd_relu = g.post_fwd && g.post.kind == 2 && !g.pre_out && !g.ep_mask;
-        if (!fwd_relu && (!g.ep_mask || g.post_fwd || g.post.alpha_len > 256 || (g.taps == 1 && g.post.alpha_sel >= 0))) return false;
+        const bool epm = g.ep_mask || g.ep_bits;       // (the bit form of the kind-2 mask counts as the mask operand)
+        const bool fwd_relu = g.post_fwd && g.post.kind == 2 && !g.pre_out && !epm;
+        if (!fwd_relu && (!epm || g.post_fwd || g.post.alpha_len > 256 || (g.taps == 1 && g.post.alpha_sel >= 0))) return false;
     }
     *o = g;
     if (g.taps == 1) {
@@ -1340,14 +1405,11 @@ int run16_point(const T *in, const uint4 *wq, const float *bias, T *out, GemmGeo
     const unsigned in_bytes = (unsigned)((long long)g.batch * g.in_sn * 2);
     const unsigned out_bytes = (unsigned)((long long)g.M * g.out_ss * 2);
 #define QK_GO(NKC, E, W) hipLaunchKernelGGL((k_hgemm16_point<T, NKC, E, W>), dim3(blocks), dim3(512), 0, stream, in, wq, bias, out, g, n_tiles, n_units, in_bytes, out_bytes)
-    const bool epm = g.ep_mask != nullptr;
-    if (wide) {
-        if (g.Q == 64) { if (epm) QK_GO(2, true, 2); else QK_GO(2, false, 2); }
-        else           { if (epm) QK_GO(1, true, 2); else QK_GO(1, false, 2); }
-    } else {
-        if (g.Q == 64) { if (epm) QK_GO(2, true, 1); else QK_GO(2, false, 1); }
-        else           { if (epm) QK_GO(1, true, 1); else QK_GO(1, false, 1); }
-    }
+    const int epm = g.ep_bits ? 2 : g.ep_mask ? 1 : 0;
+#define QK_GO3(NKC, W) do { if (epm == 2) QK_GO(NKC, 2, W); else if (epm == 1) QK_GO(NKC, 1, W); else QK_GO(NKC, 0, W); } while (0)
+    if (wide) { if (g.Q == 64) QK_GO3(2, 2); else QK_GO3(1, 2); }
+    else      { if (g.Q == 64) QK_GO3(2, 1); else QK_GO3(1, 1); }
+#undef QK_GO3
 #undef QK_GO
     return hipGetLastError() == hipSuccess ? 1 : QK_ERR_LAUNCH;
 }
@@ -1364,7 +1426,12 @@ int run16_band(const T *in, const uint4 *wq, const T *zero_line, const float *bi
 #define QK_GO(C, E, P) hipLaunchKernelGGL((k_hgemm16_band<T, WM, WN, KIN, C, TRIM, E, P, PAD>), grid, dim3(NTHR), (g.ablate & 64) ? 40960 : 0, stream, in, wq, zero_line, bias, out, g)      /* (ablate 64: profiling, ONE workgroup per CU) */
     const bool epm = g.ep_mask != nullptr, pf = g.post.kind != 0 && g.post_fwd != 0;
     if (g.sign_tbl != kSignConj) return QK_ERR_LAUNCH;                 // go16 folds the plain table into the kernel
-    if (epm) QK_GO(true, true, false); else if (pf) QK_GO(true, false, true); else QK_GO(true, false, false);
+    // bit-packed mask: the 4-wave forms only (the 8-wave tilings are an A/B switch, hgemm16_bits_route sends them down the 16-bit-mask road)
+    if constexpr (!PAD && WM * WN == 4) {
+        if (g.ep_bits) { QK_GO(true, 2, false); return hipGetLastError() == hipSuccess ? 1 : QK_ERR_LAUNCH; }
+    }
+    if (g.ep_bits || ((PAD || WM * WN != 4) && g.bits_out)) return QK_ERR_UNSUPPORTED;
+    if (epm) QK_GO(true, 1, false); else if (pf) QK_GO(true, 0, true); else QK_GO(true, 0, false);
 #undef QK_GO
     return hipGetLastError() == hipSuccess ? 1 : QK_ERR_LAUNCH;
 }
@@ -1404,6 +1471,10 @@ int go16(const void *in, const void *mask, const float *w, const float *bias, vo
     const int Cq = transposed ? g.J : g.Q, F = transposed ? g.Q : g.J;
     g.Qp = pad32(g.Q); g.Jp = pad32(g.J);
     const bool padded = g.Qp != g.Q || g.Jp != g.J;      // multiples of 16 only: the band kernel's PAD form or nothing (the caller goes on to the fp32-MFMA kernels)
+    // bit-packed kind-2 mask (GemmGeom::bits_out / ep_bits): written by the band kernels' forward epilogue, read by the band and the
+    // point kernels' backward-data epilogue, unpadded forms only -- everything else says so instead of taking another road
+    const bool bits = g.bits_out || g.ep_bits;
+    if (bits && (padded || g.post.kind != 2)) return QK_ERR_UNSUPPORTED;
     GemmGeom bg;
     {
         // 16 / 32 channels per component (start_filter = 16 models): the streaming small-channel kernel (qk_hconv16_small.hip).  Such a
@@ -1448,6 +1519,7 @@ int go16(const void *in, const void *mask, const float *w, const float *bias, vo
     const uint4 *wq4 = reinterpret_cast<const uint4 *>(wq);
     const T *zero_line = wq + total;                 // 256 zeroed bytes behind the re-laid-out kernel
     if (!padded && !(debug_flags() & kDbgNoPoint16) && point_geom(g, &bg)) {
+        if (g.bits_out) return QK_ERR_UNSUPPORTED;   // (the point form's forward epilogue writes no bits)
         note_path(QK_PATH_MFMA16_POINT);
         return run16_point<T>((const T *)in, wq4, bias, (T *)out, bg, stream);
     }
@@ -1481,6 +1553,7 @@ int go16(const void *in, const void *mask, const float *w, const float *bias, vo
         return w8 ? run16_band<T, 8, 1, 3, false>(ip, wq4, zero_line, bias, op, bg, stream)
                   : run16_band<T, 4, 1, 3, true>(ip, wq4, zero_line, bias, op, bg, stream);
     }
+    if (bits) return QK_ERR_UNSUPPORTED;
     note_path(QK_PATH_MFMA16);
     if (g.isp[0] == 1 && g.ks[0] > 1 && g.batch > 1 && g.osp[0] > 1) {       // see GemmGeom::o0_major
         g.o0_major = g.batch;
@@ -1511,6 +1584,23 @@ int launch_prep_w16_batch(int dtype, const PrepJobs &jobs, int n, hipStream_t st
     else if (dtype == QK_F16) hipLaunchKernelGGL((k_prep_w16_batch<f16>), grid, dim3(256), 0, stream, jobs);
     else return QK_ERR_INVALID_ARG;
     return hipGetLastError() == hipSuccess ? 0 : QK_ERR_LAUNCH;
+}
+
+// Which kernel a call with a bit-packed mask would reach (go16's decisions, without launching): 2 = band, 1 = point, 0 = neither
+// (then such a call is QK_ERR_UNSUPPORTED).  `g` as the call would build it, ep_mask / ep_bits / bits_out included.
+int hgemm16_bits_route(int dtype, const GemmGeom &g_in)
+{
+    if (dtype != QK_BF16 && dtype != QK_F16) return 0;
+    GemmGeom g = g_in, bg;
+    if (g.in_sc != 1 || g.out_sc != 1) return 0;
+    const long long S = (long long)g.osp[0] * g.osp[1] * g.osp[2];
+    if (g.out_sn != S * g.out_ss || g.Q % 32 != 0 || g.J % 32 != 0) return 0;
+    if (g.taps > 32 || g.pd[0] != 1 || g.pd[1] != 1 || g.pd[2] != 1) return 0;
+    if ((debug_flags() & kDbgNoMfma16) || g.post.kind != 2) return 0;
+    g.Qp = g.Q; g.Jp = g.J;
+    if (!(debug_flags() & kDbgNoPoint16) && point_geom(g, &bg)) return g.bits_out ? 0 : 1;
+    if (!(debug_flags() & (kDbgNoBand16 | kDbgBand8Waves)) && band_geom(g, 2, &bg)) return 2;
+    return 0;
 }
 
 // Returns 1 when the 16-bit MFMA path took the call, 0 when the shape is outside its fast path

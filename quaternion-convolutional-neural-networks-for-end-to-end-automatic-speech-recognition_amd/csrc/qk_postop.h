@@ -118,6 +118,49 @@ __device__ __forceinline__ uint4 post_bwd8_relu(const uint4 &dy, const uint4 &y,
     return make_uint4(out[0], out[1], out[2], out[3]);
 }
 
+// ---- bit-packed form of the kind-2 mask (include/qk.h: qk_conv_fwd_post_bits) ----------------------------------------
+// Bit i of the bit tensor belongs to flat channels-last element i of y: byte i >> 3, bit i & 7 -- a 16-byte piece of 8
+// consecutive elements is ONE byte.  The bit IS the predicate of post_bwd8_relu above, `y > 0.f` on the widened value
+// (NaN and -0: clear; subnormals and +inf: set), evaluated once by the producer instead of by every consumer.
+template <typename T>
+__device__ __forceinline__ unsigned gt0_bits8(const uint4 &y)
+{
+    const unsigned q[4] = {y.x, y.y, y.z, y.w};
+    unsigned bits = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float ya, yb;
+        unpack2<T>(q[k], ya, yb);
+        bits |= (ya > 0.f ? 1u : 0u) << (2 * k) | (yb > 0.f ? 1u : 0u) << (2 * k + 1);
+    }
+    return bits;
+}
+// keep the 16-bit halves of the 8 packed elements whose bit is set (bit e = element e: half e & 1 of dword e >> 1)
+__device__ __forceinline__ uint4 keep_bits8(const uint4 &v, unsigned bits)
+{
+    unsigned in[4] = {v.x, v.y, v.z, v.w}, out[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned two = (bits >> (2 * k)) & 3u;
+        out[k] = in[k] & (((two & 1u) | ((two & 2u) << 15)) * 0xffffu);
+    }
+    return make_uint4(out[0], out[1], out[2], out[3]);
+}
+// post_bwd8_relu with the predicate read from the bit tensor: the same two roundings of dy (the caller packed it to 16 bits;
+// scaled in fp32 and packed again here), +0 where the bit is clear
+template <typename T>
+__device__ __forceinline__ uint4 post_bwd8_relu_bits(const uint4 &dy, unsigned bits, float scale)
+{
+    unsigned g[4] = {dy.x, dy.y, dy.z, dy.w}, out[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float ga, gb;
+        unpack2<T>(g[k], ga, gb);
+        out[k] = repack2(T(), ga * scale, gb * scale);
+    }
+    return keep_bits8(make_uint4(out[0], out[1], out[2], out[3]), bits);
+}
+
 template <typename T>
 __device__ __forceinline__ uint4 post_bwd8(const uint4 &dy, const uint4 &pre, float alpha, unsigned idx, const PostOp &p, float &dal)
 {

@@ -265,22 +265,39 @@ class _Call(object):
         return dw, db
 
 
-    def fwd_post(self, x, w, bias, post, wparam=None):
+    def mask_bits_bytes(self):
+        """Bytes of the bit-packed relu mask this layer's forward can write beside y (qk_conv_mask_bits_bytes), 0: it cannot."""
+        return int(L.lib().qk_conv_mask_bits_bytes(ctypes.byref(self.desc)))
+
+    def reads_mask_bits(self):
+        """True when this layer's backward-data can read the bit-packed mask of its input (qk_conv_bwd_reads_mask_bits)."""
+        return bool(L.lib().qk_conv_bwd_reads_mask_bits(ctypes.byref(self.desc)))
+
+    def fwd_post(self, x, w, bias, post, wparam=None, bits_bytes=0):
         """(pre, y) = qk_conv_fwd_post: the LINEAR convolution and post(pre) (PReLU / dropout) from one launch.  The relu
-        form of the post-op (post.alpha is None) writes y only: pre is None."""
+        form of the post-op (post.alpha is None) writes y only: pre is None.  bits_bytes > 0 (relu form): returns
+        (bits, y) instead, bits the uint8 bit-packed mask y > 0 (qk_conv_fwd_post_bits)."""
         pre = torch.empty(self.y_shape, dtype=x.dtype, device=x.device) if post.alpha is not None else None
         y = torch.empty(self.y_shape, dtype=x.dtype, device=x.device)
         ws, n = self._ws(L.QK_OP_FWD, x, wparam)
+        if bits_bytes:
+            bits = torch.empty(bits_bytes, dtype=torch.uint8, device=x.device)
+            with _on_device(x.device):
+                rc = L.lib().qk_conv_fwd_post_bits(ctypes.byref(self.desc), ctypes.byref(post.struct), _ptr(x), _ptr(w), _ptr(bias),
+                                                   None, _ptr(y), _ptr(bits), _ptr(ws), n, _stream(x))
+            L.check(rc, 'qk_conv_fwd_post_bits')
+            return bits, y
         with _on_device(x.device):
             rc = L.lib().qk_conv_fwd_post(ctypes.byref(self.desc), ctypes.byref(post.struct), _ptr(x), _ptr(w), _ptr(bias),
                                           _ptr(pre), _ptr(y), _ptr(ws), n, _stream(x))
         L.check(rc, 'qk_conv_fwd_post')
         return pre, y
 
-    def bwd_post(self, x, dy, w, has_bias, post_x, x_pre, dalpha_x, direct=None, wparam=None):
+    def bwd_post(self, x, dy, w, has_bias, post_x, x_pre, dalpha_x, direct=None, wparam=None, x_bits=None):
         """Fused backward of a LINEAR layer whose input x = post_x(x_pre): returns (d x_pre, dw, db) and accumulates
         the slope gradient of post_x into dalpha_x (qk_conv_bwd_post).  direct = (dw, db) buffers to ADD into
-        (QK_BWD_ACCUMULATE; the returned dw / db are then None).  Relu form of post_x: x_pre / dalpha_x are None."""
+        (QK_BWD_ACCUMULATE; the returned dw / db are then None).  Relu form of post_x: x_pre / dalpha_x are None, and
+        x_bits (fwd_post's bit-packed mask of x) replaces reading x as the mask (qk_conv_bwd_post_bits)."""
         dx = torch.empty(self.x_shape, dtype=dy.dtype, device=dy.device)
         if direct is not None:
             dw, db = direct
@@ -288,6 +305,13 @@ class _Call(object):
             dw = torch.empty(self.w_shape, dtype=torch.float32, device=x.device)
             db = torch.empty((self.w_shape[-1],), dtype=torch.float32, device=x.device) if has_bias else None
         ws, n = self._ws(L.QK_OP_BWD, x, wparam)
+        if x_bits is not None:
+            with _on_device(x.device):
+                rc = L.lib().qk_conv_bwd_post_bits(ctypes.byref(self.desc), _ptr(x), _ptr(x_bits), _ptr(dy), _ptr(w), _ptr(dx), _ptr(dw),
+                                                   _ptr(db), ctypes.byref(post_x.struct), L.QK_BWD_ACCUMULATE if direct is not None else 0,
+                                                   _ptr(ws), n, _stream(x))
+            L.check(rc, 'qk_conv_bwd_post_bits')
+            return (dx, None, None) if direct is not None else (dx, dw, db)
         with _on_device(x.device):
             rc = L.lib().qk_conv_bwd_post(ctypes.byref(self.desc), _ptr(x), _ptr(dy), _ptr(w), _ptr(dx), _ptr(dw), _ptr(db),
                                           ctypes.byref(post_x.struct), _ptr(x_pre), _ptr(dalpha_x),
@@ -963,12 +987,20 @@ class _ConvChainFn(torch.autograd.Function):
         n = len(calls)
         ws, bs, alphas = params[:n], params[n:2 * n], params[2 * n:]
         acts, pres = [x], []
-        for call, w, b, post in zip(calls, ws, bs, posts):
+        # Bit-packed relu masks: link i -> i + 1 uses them when layer i has the relu-form post-op, its forward kernel can write the
+        # bits and layer i + 1's backward-data can read them -- decided here, once, from both descriptors; pres[i] then holds the
+        # bits (the relu form has no pre-activation to save).  The last link's own post-op has no consumer in the chain.
+        no_bits = L.dbg(L.QK_DBG_NO_MASK_BITS)
+        bits_bytes = [0] * n
+        for i in range(n - 1):
+            if posts[i] is not None and posts[i].alpha is None and not no_bits and calls[i + 1].reads_mask_bits():
+                bits_bytes[i] = calls[i].mask_bits_bytes()
+        for i, (call, w, b, post) in enumerate(zip(calls, ws, bs, posts)):
             if post is None:
                 acts.append(call.fwd(acts[-1], w, b, wparam=w))
                 pres.append(None)
             else:
-                pre, y = call.fwd_post(acts[-1], w, b, post, wparam=w)
+                pre, y = call.fwd_post(acts[-1], w, b, post, wparam=w, bits_bytes=bits_bytes[i])
                 acts.append(y)
                 pres.append(pre)
         if chain_tap is not None:
@@ -1000,8 +1032,9 @@ class _ConvChainFn(torch.autograd.Function):
             pw, pb = ctx.param_refs[0][i], ctx.param_refs[1][i]
             direct = _direct_grad(pw, pb, ctx.needs_input_grad[3 + i], ctx.has_bias[i] and ctx.needs_input_grad[3 + n + i])
             if i > 0 and posts[i - 1] is not None:
-                g, dws[i], dbs[i] = calls[i].bwd_post(acts[i], g, ws[i], ctx.has_bias[i], posts[i - 1], pres[i - 1], das[i - 1],
-                                                      direct=direct, wparam=pw)
+                relu_form = posts[i - 1].alpha is None                 # (then pres[i - 1] is the bit-packed mask of acts[i], or None)
+                g, dws[i], dbs[i] = calls[i].bwd_post(acts[i], g, ws[i], ctx.has_bias[i], posts[i - 1], None if relu_form else pres[i - 1],
+                                                      das[i - 1], direct=direct, wparam=pw, x_bits=pres[i - 1] if relu_form else None)
                 if direct is not None:
                     _grad_ready(pw, pb)
                 continue
