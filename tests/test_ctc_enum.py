@@ -80,7 +80,8 @@ def test_recursion_restatements_equal_the_enumerated_cost_and_gradient(case):
 @pytest.mark.parametrize('case', CASES, ids=IDS)
 def test_fused_ctc_kernels_equal_the_enumerated_cost_and_gradient(case, form, dtype):
     """qk_ctc_batch_cost (csrc/qk_ctc.hip: k_ctc_fast and the two-sweep k_ctc) against the enumeration on the operands the kernel
-    sees (posteriors rounded to the activation dtype first)."""
+    sees (posteriors rounded to the activation dtype first).
+    (Every gradient entry against its own bound, at larger lattices: tests/test_head_elementwise.py.)"""
     if not torch.cuda.is_available():
         pytest.skip('needs a GPU')
     from qcnn_amd import _lib

@@ -381,7 +381,8 @@ def test_tall_dense_split_reduction_matches_plain_autograd():
 def test_fused_ctc_batch_cost_matches_the_keras_restatement(shape, dtype):
     """qk_ctc_batch_cost (K.ctc_batch_cost of interspeech_model.py:37-39 as one launch: cost and d cost / d y_pred) against the
     torch restatement of the Keras / TensorFlow op that the golden fixture G17 pins (layers.ctc_batch_cost with the fused path
-    off): ragged input and label lengths, repeated labels, an empty label sequence, frames past the input length."""
+    off): ragged input and label lengths, repeated labels, an empty label sequence, frames past the input length.
+    (Every gradient entry against its own bound: tests/test_head_elementwise.py.)"""
     if not torch.cuda.is_available():
         pytest.skip('needs a GPU')
     dev = torch.device('cuda:0')
@@ -423,7 +424,8 @@ def test_fused_ctc_batch_cost_matches_the_keras_restatement(shape, dtype):
 def test_fused_dense_softmax_output_layer_matches_float64(dtype, rows, kin, units):
     """TimeDistributed(Dense(62, activation='softmax')) (interspeech_model.py:171-175) through layers._DenseSoftmaxFn -- library
     GEMMs + qk_softmax_rows_fwd / _bwd -- against a float64 restatement on the same 16-bit operands: posteriors, d input,
-    d kernel, d bias; with the bench's weighted-sum loss (qk_weighted_sum) on top.  Also against the unfused torch path."""
+    d kernel, d bias; with the bench's weighted-sum loss (qk_weighted_sum) on top.  Also against the unfused torch path.
+    (Element by element, at the kernel's tile edges: tests/test_head_elementwise.py.)"""
     if not torch.cuda.is_available():
         pytest.skip('needs a GPU')
     import qcnn_amd
