@@ -45,8 +45,18 @@ phone's first frame, qcnn_amd.features.frames_to_samples).  Nobody has measured 
 --confusions N (0 = off) adds to every evaluation the split of the 39-class errors of ALL held-out batches into %cor / %sub / %del /
 %ins (of the reference phones, as sclite prints them; TimitQCNN.error_breakdown) and the N largest confusion pairs of the 39-class
 matrix, which is accumulated on the device over the batches (`<ins>` / `<del>` stand for the missing partner).
+
+--warmup N, --lr-decay {inverse-time,exponential,cosine,inv-sqrt} (with --decay-steps, --decay-rate, --lr-floor), --ema D,
+--halve-on-plateau (with --plateau-patience), --checkpoint PATH and --resume PATH switch the optimiser step to
+qcnn_amd.training.ScheduledAdam: the rate of every step is formed on the device from the step counter (--lr is the base rate;
+cosine decays over --steps), with --ema an exponential moving average of the weights is kept and every evaluation runs with the
+AVERAGED weights (the log line says so), with --halve-on-plateau the rate is halved whenever the held-out PER(39) has not improved
+for more than --plateau-patience evaluations (newbob), and every log line shows the rate of the last applied step.  --checkpoint
+writes model, optimiser, augmentation counters, step and batch-order state at every evaluation; --resume continues from such a file
+(give the same options; under cosine that includes --steps, which is the schedule's length).  It combines with the guard options above.  No phone error rate has been measured with any of them.
 """
 import argparse
+import contextlib
 import fractions
 import os
 import sys
@@ -63,7 +73,7 @@ from qcnn_amd.features import (NoiseReverb, SpecAugment, SpeedPerturb, frames_to
                                synthetic_rirs)
 from qcnn_amd.lm import NgramLM  # noqa: E402
 from qcnn_amd.models import getTimitModel2D  # noqa: E402
-from qcnn_amd.training import GradGuard  # noqa: E402
+from qcnn_amd.training import GradGuard, LRSchedule, ReduceOnPlateau, ScheduledAdam, load_checkpoint, save_checkpoint  # noqa: E402
 
 
 def load_split(root, boundaries=False):
@@ -202,6 +212,19 @@ def main():
                     help='at every evaluation, force-align the held-out batch and print the share of boundaries within 20 ms of the .PHN ones')
     ap.add_argument('--confusions', type=int, default=0, metavar='N',
                     help='at every evaluation, print %%cor / %%sub / %%del / %%ins of all held-out batches and the top N confusion pairs (0 = off)')
+    ap.add_argument('--warmup', type=int, default=0, metavar='N', help='linear warm-up of the learning rate over the first N steps (0: off)')
+    ap.add_argument('--lr-decay', default='none', choices=['none', 'inverse-time', 'exponential', 'cosine', 'inv-sqrt'],
+                    help='learning-rate schedule behind the warm-up, evaluated on the device (cosine: over --steps)')
+    ap.add_argument('--decay-steps', type=int, default=1000, help='exponential: steps per factor of --decay-rate')
+    ap.add_argument('--decay-rate', type=float, default=None,
+                    help='inverse-time: the decay= of Keras\' Adam (default 1e-4); exponential: the factor per --decay-steps (default 0.5)')
+    ap.add_argument('--lr-floor', type=float, default=0.0, help='cosine: share of --lr the schedule ends at')
+    ap.add_argument('--ema', type=float, default=0.0, metavar='D',
+                    help='keep an exponential moving average of the weights with decay D and evaluate with it (0: off)')
+    ap.add_argument('--halve-on-plateau', action='store_true', help='halve the rate when the held-out PER(39) stops improving')
+    ap.add_argument('--plateau-patience', type=int, default=0, help='evaluations without improvement that are tolerated')
+    ap.add_argument('--checkpoint', default=None, metavar='PATH', help='write a checkpoint at every evaluation')
+    ap.add_argument('--resume', default=None, metavar='PATH', help='continue from a checkpoint written by --checkpoint')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
@@ -255,28 +278,56 @@ def main():
         guard = GradGuard(dev, clipnorm=args.clipnorm, clipvalue=args.clipvalue, dynamic=args.dynamic_loss_scale,
                           loss_scale=2.0 ** 12 if dtype == torch.float16 or args.dynamic_loss_scale else 1.0)
         step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-    for step in range(1, args.steps + 1):
+    # warm-up / decay / averaged weights / plateau halving / checkpoints: the scheduled step (qcnn_amd.training.ScheduledAdam).  The
+    # rate is formed on the device from the step counter; the guard, when there is one, runs in front of it.
+    opt = plateau = None
+    first_step = 1
+    if (args.warmup > 0 or args.lr_decay != 'none' or args.ema > 0 or args.halve_on_plateau or args.checkpoint or args.resume):
+        kind = 'constant' if args.lr_decay == 'none' else args.lr_decay
+        rate = args.decay_rate if args.decay_rate is not None else {'inverse-time': 1e-4, 'exponential': 0.5}.get(kind, 1.0)
+        schedule = LRSchedule(args.lr, kind, warmup_steps=args.warmup, total_steps=args.steps if kind == 'cosine' else 0, decay_steps=args.decay_steps, rate=rate,
+                              floor=args.lr_floor)
+        opt = ScheduledAdam(flat.param, flat.grad, schedule, guard=guard, ema_decay=args.ema)
+        plateau = ReduceOnPlateau(patience=args.plateau_patience) if args.halve_on_plateau else None
+        policies = [q for q in (augment,) + (wave_augment if isinstance(wave_augment, tuple) else (wave_augment,)) if q is not None]
+        if args.resume:
+            extra = load_checkpoint(args.resume, model, opt, policies)
+            first_step = extra['step'] + 1
+            rng.set_state(('MT19937', extra['rng_keys'].numpy().astype(np.uint32), extra['rng_pos'], 0, 0.0))
+            if plateau is not None and extra['plateau'] is not None:
+                plateau.load_state_dict(extra['plateau'])
+            print('resumed from %s at step %d (%d applied)' % (args.resume, extra['step'], opt.stats()['step']))
+    eval_weights = opt.averaged if opt is not None and args.ema > 0 else contextlib.nullcontext
+    for step in range(first_step, args.steps + 1):
         x, il, labels, ll = to_device(train, batches[rng.randint(len(batches))], dev, dtype, augment, wave_augment)
         if guard is None:
             loss = model.training_loss(x, labels, il, ll)
-            loss.backward()
-            F.adam_step(flat.param, flat.grad, m, v, step, lr=args.lr, zero_grad=True)
         else:
             loss = model.training_loss(x, labels, il, ll, loss_scale=guard.loss_scale)
-            loss.backward()
+        loss.backward()
+        if opt is not None:
+            opt.step(zero_grad=True)
+        elif guard is None:
+            F.adam_step(flat.param, flat.grad, m, v, step, lr=args.lr, zero_grad=True)
+        else:
             guard.step(flat.param, flat.grad, m, v, step_dev, lr=args.lr, zero_grad=True)
         if step == 1 or step % 50 == 0 or step == args.steps:
-            if guard is None:
-                print('step %5d  loss %.4f' % (step, float(loss)))
-            else:
+            line = 'step %5d  loss %.4f' % (step, float(loss))
+            if guard is not None:
                 s = guard.stats()                                     # (the one host read of the guard, at log lines only)
-                print('step %5d  loss %.4f  grad norm %.4g  loss scale %g  skipped %d'
-                      % (step, float(loss), s['last_norm'], s['scale'], s['skipped_steps']))
-        if args.eval_every > 0 and step % args.eval_every == 0 and held_out is not None:
+                line += '  grad norm %.4g  loss scale %g  skipped %d' % (s['last_norm'], s['scale'], s['skipped_steps'])
+            if opt is not None:
+                s = opt.stats()                                       # (likewise)
+                line += '  lr %.4g' % s['last_lr'] + ('  ema decay %.4g' % s['last_ema_decay'] if args.ema > 0 else '')
+            print(line)
+        if not (args.eval_every > 0 and step % args.eval_every == 0 and held_out is not None):
+            continue
+        with eval_weights():                                          # --ema: param and ema change places for the evaluation
             xe, ile, le, lle = to_device(test, held_out, dev, dtype)
             res = model.evaluate(xe, le, ile, lle, class_map=class_map)
-            print('step %5d  held-out ctc cost %.4f  PER(39) %.4f (%d / %d)'
-                  % (step, float(res.loss), float(res.per), int(res.errors), int(res.symbols)))
+            print('step %5d  held-out ctc cost %.4f  PER(39) %.4f (%d / %d)%s'
+                  % (step, float(res.loss), float(res.per), int(res.errors), int(res.symbols),
+                     '  [averaged weights, ema %g]' % args.ema if opt is not None and args.ema > 0 else ''))
             if args.align_eval:
                 ali = model.align(xe, le, ile, lle)
                 hits, total, share = layers.boundary_agreement(frames_to_samples(ali.starts), reference_starts(test, held_out, le.shape[1], dev),
@@ -300,6 +351,14 @@ def main():
                                        lm_weight=args.lm_weight, insertion_bonus=args.insertion_bonus)
                 print('step %5d  held-out beam %d PER(39) without LM %.4f  with %d-gram LM %.4f'
                       % (step, args.beam_width, float(plain.per), args.lm_order, float(fused.per)))
+        if plateau is not None:
+            opt.set_lr_scale(plateau.update(float(res.per)))
+            print('step %5d  learning-rate scale %g' % (step, plateau.scale))
+        if args.checkpoint:
+            state = rng.get_state()
+            save_checkpoint(args.checkpoint, model, opt, policies,
+                            extra=dict(step=step, plateau=plateau.state_dict() if plateau is not None else None,
+                                       rng_keys=torch.from_numpy(state[1].astype(np.int64)), rng_pos=int(state[2])))
 
 
 if __name__ == '__main__':

@@ -195,6 +195,30 @@ SYMBOLS = {
                                             ctypes.c_float, _VP, I32, _GC, _VP, _VP]),
 }
 
+# ---- include/qk_opt.h: the scheduled optimiser step (a second table: SYMBOLS stays the inventory of include/qk.h) ----
+QK_LR_CONSTANT, QK_LR_INVERSE_TIME, QK_LR_EXPONENTIAL, QK_LR_COSINE, QK_LR_INV_SQRT = 0, 1, 2, 3, 4
+QK_LR_KINDS = {'constant': QK_LR_CONSTANT, 'inverse-time': QK_LR_INVERSE_TIME, 'exponential': QK_LR_EXPONENTIAL,
+               'cosine': QK_LR_COSINE, 'inv-sqrt': QK_LR_INV_SQRT}
+
+
+class LRScheduleDesc(ctypes.Structure):
+    """qk_lr_schedule_t (include/qk_opt.h)"""
+    _fields_ = [('base_lr', ctypes.c_double), ('kind', I32), ('warmup_steps', I32), ('total_steps', I32), ('decay_steps', I32),
+                ('rate', ctypes.c_double), ('floor', ctypes.c_double)]
+
+
+# qk_opt_state_t: eight 4-byte words in device memory; (name, is_float) in order
+OPT_STATE = (('lr_scale', True), ('last_lr', True), ('last_ema_decay', True), ('ema_updates', False),
+             ('reserved0', False), ('reserved1', False), ('reserved2', False), ('reserved3', False))
+_LS = ctypes.POINTER(LRScheduleDesc)
+
+OPT_SYMBOLS = {
+    'qk_adam_step_sched': (ctypes.c_int, [_FP, _FP, _FP, _FP, _FP, _FP, _SZ, _LS, ctypes.c_float, I32, ctypes.c_float, ctypes.c_float,
+                                          ctypes.c_float, ctypes.c_float, _VP, I32, _GC, _VP, _VP, _VP]),
+    'qk_swap_f32': (ctypes.c_int, [_FP, _FP, _SZ, _VP]),
+    'qk_lr_schedule_value': (ctypes.c_int, [_LS, ctypes.c_int64, ctypes.c_float, ctypes.POINTER(ctypes.c_float)]),
+}
+
 _lib = None
 
 
@@ -207,9 +231,10 @@ def lib():
                 'libqk_hip.so is not built (%s). Run `python -c "import __graft_entry__ as g; '
                 'g.build()"` -- the quaternion layers have no CPU or eager fallback.' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
+        for table in (SYMBOLS, OPT_SYMBOLS):
+            for name, (res, args) in table.items():
+                fn = getattr(handle, name)
+                fn.restype, fn.argtypes = res, args
         _lib = handle
     return _lib
 

@@ -777,6 +777,62 @@ def adam_step_guarded(param, grad, m, v, step, config, state, lr=0.001, beta1=0.
         refresh_prepped_kernels(param)
 
 
+def _opt_state_ok(what, state, device):
+    if (not isinstance(state, torch.Tensor) or state.dtype != torch.float32 or state.numel() != len(L.OPT_STATE)
+            or not state.is_contiguous() or state.device != device):
+        raise TypeError('%s: opt_state must be the %d-element float32 device block of qk_opt_state_t on the buffers\' device'
+                        % (what, len(L.OPT_STATE)))
+
+
+def adam_step_sched(param, grad, m, v, step, schedule, opt_state, guard_config=None, guard_state=None, ema=None, ema_decay=0.0,
+                    ema_warmup=True, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, zero_grad=False, decay=None):
+    """adam_step(step=<device tensor>) / adam_step_guarded whose rate is the schedule's (qk_adam_step_sched, include/qk_opt.h):
+    lr_eff = base_lr * w(t) * f(t) * opt_state.lr_scale, formed on the device from the step counter, so that no launch argument
+    depends on the step.  schedule: a _lib.LRScheduleDesc; opt_state: the 8-element float32 device block that holds
+    qk_opt_state_t (training.ScheduledAdam owns one).  guard_config / guard_state: both None (plain step, with grad_scale) or
+    both given (the step grad_guard_reduce decided on; grad_scale must be 1).  ema: optional flat buffer that follows param with
+    decay `ema_decay` (warmed up as TensorFlow's ExponentialMovingAverage does when ema_warmup).  A skipped step writes nothing
+    but the cleared gradient.  Nothing is read on the host."""
+    _flat_f32('adam_step_sched', param, grad, m, v, decay, ema)
+    _opt_state_ok('adam_step_sched', opt_state, param.device)
+    if (guard_config is None) != (guard_state is None):
+        raise ValueError('adam_step_sched: guard_config and guard_state go together')
+    if guard_state is not None:
+        _guard_state_ok('adam_step_sched', guard_state, param.device)
+        if grad_scale != 1.0:
+            raise ValueError('adam_step_sched: grad_scale must be 1 with a guard (grad_guard_reduce already applied it)')
+    if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or not step.is_cuda or step.numel() != 1:
+        raise TypeError('adam_step_sched: the step counter must be a one-element int32 device tensor (the rate is a function of it)')
+    n = param.numel()
+    for name, t in (('grad', grad), ('m', m), ('v', v), ('decay', decay), ('ema', ema)):
+        if t is not None and t.numel() != n:
+            raise ValueError('adam_step_sched: %s must have one element per parameter element' % name)
+    with _on_device(param.device):
+        rc = L.lib().qk_adam_step_sched(_ptr(param), _ptr(grad), _ptr(m), _ptr(v), _ptr(decay), _ptr(ema), n, ctypes.byref(schedule),
+                                        ema_decay, int(bool(ema_warmup)), beta1, beta2, eps, grad_scale, _ptr(step),
+                                        int(bool(zero_grad)), ctypes.byref(guard_config) if guard_config is not None else None,
+                                        _ptr(guard_state), _ptr(opt_state), _stream(param))
+    L.check(rc, 'qk_adam_step_sched')
+    torch.autograd.graph.increment_version(param)
+    if _PREP_CACHE_ON:
+        refresh_prepped_kernels(param)
+
+
+def swap_(a, b):
+    """Exchange the contents of two flat float32 device buffers in place, in one launch (qk_swap_f32); they must not overlap.
+    Moves both version counters and brings the cached 16-bit kernel images of parameters living in either up to date."""
+    _flat_f32('swap_', a, b)
+    if a.numel() != b.numel() or a.device != b.device:
+        raise ValueError('swap_: the buffers must have the same number of elements and live on one device')
+    with _on_device(a.device):
+        rc = L.lib().qk_swap_f32(_ptr(a), _ptr(b), a.numel(), _stream(a))
+    L.check(rc, 'qk_swap_f32')
+    for t in (a, b):
+        torch.autograd.graph.increment_version(t)
+        if _PREP_CACHE_ON:
+            refresh_prepped_kernels(t)
+
+
 class _MaxPoolCL(torch.autograd.Function):
     """qk_maxpool2d_fwd / _bwd on a channels_last buffer (N, H, W, C); windows == strides."""
 
