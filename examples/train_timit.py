@@ -54,6 +54,13 @@ AVERAGED weights (the log line says so), with --halve-on-plateau the rate is hal
 for more than --plateau-patience evaluations (newbob), and every log line shows the rate of the last applied step.  --checkpoint
 writes model, optimiser, augmentation counters, step and batch-order state at every evaluation; --resume continues from such a file
 (give the same options; under cosine that includes --steps, which is the schedule's length).  It combines with the guard options above.  No phone error rate has been measured with any of them.
+
+--device-corpus packs TRAIN and TEST once into device memory (qcnn_amd.data.DeviceCorpus) and takes every training batch from
+DeviceCorpus.next_batch: one launch gathers the padded waveforms, lengths and labels of the next row of an EpochSampler, whose
+order is a keyed permutation of the length-sorted batches evaluated on the device -- real epochs (every batch once per epoch, a new
+order each epoch; the log line shows the epoch) in place of draws with replacement, and no per-step host assembly or copy.  Held-out
+batches come from DeviceCorpus.batch.  The sampler's position is saved with the augmentation counters by --checkpoint.  Without the
+flag the script behaves exactly as before.
 """
 import argparse
 import contextlib
@@ -68,7 +75,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.realpath(__file__))))
 import qcnn_amd  # noqa: E402,F401
 from qcnn_amd import dp, functional as F, layers  # noqa: E402
-from qcnn_amd.data import TIMIT_PHONES_39, TIMIT_PHONES_61, read_audio, read_phn, read_phn_segments, timit_61_to_39_class_map  # noqa: E402
+from qcnn_amd.data import DeviceCorpus, EpochSampler, TIMIT_PHONES_39, TIMIT_PHONES_61, read_audio, read_phn, read_phn_segments, timit_61_to_39_class_map  # noqa: E402
 from qcnn_amd.features import (NoiseReverb, SpecAugment, SpeedPerturb, frames_to_samples, quaternion_fbank, synthetic_noises,  # noqa: E402
                                synthetic_rirs)
 from qcnn_amd.lm import NgramLM  # noqa: E402
@@ -159,6 +166,14 @@ def to_device(utts, idx, dev, dtype, augment=None, wave_augment=None):
     return x, frame_lengths[:, None], labels, label_length
 
 
+def device_batch(parts, dtype, augment=None, wave_augment=None):
+    """to_device for a batch that a DeviceCorpus gathered (parts: what DeviceCorpus.batch / next_batch return): only the front end
+    is left to do."""
+    wave, lengths, labels, label_length = parts[:4]
+    x, frame_lengths = quaternion_fbank(wave, lengths, normalize='utterance', dtype=dtype, augment=augment, wave_augment=wave_augment)
+    return x, frame_lengths[:, None], labels, label_length
+
+
 def reference_starts(utts, idx, width, dev):
     """(B, width) int64 start samples of the batch's phones (load_split(boundaries=True)), padded with -1."""
     ref = np.full((len(idx), width), -1, dtype=np.int64)
@@ -225,6 +240,8 @@ def main():
     ap.add_argument('--plateau-patience', type=int, default=0, help='evaluations without improvement that are tolerated')
     ap.add_argument('--checkpoint', default=None, metavar='PATH', help='write a checkpoint at every evaluation')
     ap.add_argument('--resume', default=None, metavar='PATH', help='continue from a checkpoint written by --checkpoint')
+    ap.add_argument('--device-corpus', action='store_true',
+                    help='keep TRAIN and TEST in device memory, shuffle epochs and assemble every batch on the device')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
@@ -239,6 +256,24 @@ def main():
     held_out_all = length_batches(test, args.batch) if test else []
     held_out = held_out_all[0] if test else None
     class_map = torch.from_numpy(timit_61_to_39_class_map())
+    corpus = sampler = test_corpus = None
+    if args.device_corpus:
+        corpus = DeviceCorpus([u[0] for u in train], [u[1] for u in train], device=dev)
+        sampler = EpochSampler(corpus.wave_len, args.batch, seed=args.seed & 0xFFFFFFFF)
+        if test:
+            test_corpus = DeviceCorpus([u[0] for u in test], [u[1] for u in test], aux=[u[2] for u in test] if args.align_eval else None,
+                                       device=dev)
+        print('device-resident corpus: %.1f MB of waveforms, %d batches per epoch'
+              % (2e-6 * (corpus.arrays.wave_pack.numel() + (test_corpus.arrays.wave_pack.numel() if test_corpus is not None else 0)),
+                 sampler.num_batches))
+
+    def held_out_batch(idx):
+        """(features, frame counts, labels, label lengths, reference start samples or None) of a held-out batch."""
+        if test_corpus is None:
+            starts = reference_starts(test, idx, max(len(test[i][1]) for i in idx), dev) if args.align_eval else None
+            return to_device(test, idx, dev, dtype) + (starts,)
+        parts = test_corpus.batch(idx)
+        return device_batch(parts, dtype) + (parts[4].to(torch.int64) if args.align_eval else None,)
     lm = None
     if args.lm_order > 0:
         lm = NgramLM.estimate([u[1] for u in train], len(TIMIT_PHONES_61), args.lm_order)
@@ -250,7 +285,7 @@ def main():
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     model, _ = getTimitModel2D(d)
-    x0 = to_device(train, batches[0][:1], dev, dtype)[0]
+    x0 = (to_device(train, batches[0][:1], dev, dtype) if corpus is None else device_batch(corpus.batch(batches[0][:1]), dtype))[0]
     with torch.no_grad():
         model(x0)                                                 # build-on-first-call, like Keras
     model.to(dev)
@@ -289,7 +324,7 @@ def main():
                               floor=args.lr_floor)
         opt = ScheduledAdam(flat.param, flat.grad, schedule, guard=guard, ema_decay=args.ema)
         plateau = ReduceOnPlateau(patience=args.plateau_patience) if args.halve_on_plateau else None
-        policies = [q for q in (augment,) + (wave_augment if isinstance(wave_augment, tuple) else (wave_augment,)) if q is not None]
+        policies = [q for q in (augment,) + (wave_augment if isinstance(wave_augment, tuple) else (wave_augment,)) + (sampler,) if q is not None]
         if args.resume:
             extra = load_checkpoint(args.resume, model, opt, policies)
             first_step = extra['step'] + 1
@@ -299,7 +334,11 @@ def main():
             print('resumed from %s at step %d (%d applied)' % (args.resume, extra['step'], opt.stats()['step']))
     eval_weights = opt.averaged if opt is not None and args.ema > 0 else contextlib.nullcontext
     for step in range(first_step, args.steps + 1):
-        x, il, labels, ll = to_device(train, batches[rng.randint(len(batches))], dev, dtype, augment, wave_augment)
+        if sampler is None:
+            x, il, labels, ll = to_device(train, batches[rng.randint(len(batches))], dev, dtype, augment, wave_augment)
+        else:
+            epoch = sampler.epoch                                     # (the host cursor: no device read)
+            x, il, labels, ll = device_batch(corpus.next_batch(sampler), dtype, augment, wave_augment)
         if guard is None:
             loss = model.training_loss(x, labels, il, ll)
         else:
@@ -312,7 +351,7 @@ def main():
         else:
             guard.step(flat.param, flat.grad, m, v, step_dev, lr=args.lr, zero_grad=True)
         if step == 1 or step % 50 == 0 or step == args.steps:
-            line = 'step %5d  loss %.4f' % (step, float(loss))
+            line = 'step %5d  loss %.4f' % (step, float(loss)) + ('  epoch %d' % epoch if sampler is not None else '')
             if guard is not None:
                 s = guard.stats()                                     # (the one host read of the guard, at log lines only)
                 line += '  grad norm %.4g  loss scale %g  skipped %d' % (s['last_norm'], s['scale'], s['skipped_steps'])
@@ -323,21 +362,20 @@ def main():
         if not (args.eval_every > 0 and step % args.eval_every == 0 and held_out is not None):
             continue
         with eval_weights():                                          # --ema: param and ema change places for the evaluation
-            xe, ile, le, lle = to_device(test, held_out, dev, dtype)
+            xe, ile, le, lle, starts = held_out_batch(held_out)
             res = model.evaluate(xe, le, ile, lle, class_map=class_map)
             print('step %5d  held-out ctc cost %.4f  PER(39) %.4f (%d / %d)%s'
                   % (step, float(res.loss), float(res.per), int(res.errors), int(res.symbols),
                      '  [averaged weights, ema %g]' % args.ema if opt is not None and args.ema > 0 else ''))
             if args.align_eval:
                 ali = model.align(xe, le, ile, lle)
-                hits, total, share = layers.boundary_agreement(frames_to_samples(ali.starts), reference_starts(test, held_out, le.shape[1], dev),
-                                                               lle, tolerance=int(round(0.02 * 16000)))
+                hits, total, share = layers.boundary_agreement(frames_to_samples(ali.starts), starts, lle, tolerance=int(round(0.02 * 16000)))
                 print('step %5d  held-out boundary agreement within 20 ms %.4f (%d / %d)' % (step, float(share), int(hits), int(total)))
             if args.confusions > 0:
                 confusion = torch.zeros((len(TIMIT_PHONES_39) + 1,) * 2, dtype=torch.int32, device=dev)
                 parts = []
                 for idx in held_out_all:                              # one matrix, accumulated on the device over the batches
-                    xb, ilb, lb, llb = to_device(test, idx, dev, dtype)
+                    xb, ilb, lb, llb = held_out_batch(idx)[:4]
                     parts.append(model.error_breakdown(xb, lb, ilb, llb, class_map=class_map, confusion=confusion))
                 c, s, d, i = (sum(int(getattr(p, f)) for p in parts) for f in ('correct', 'substitutions', 'deletions', 'insertions'))
                 n = max(c + s + d, 1)

@@ -20,6 +20,7 @@ def _newest_header():
     deps = glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(CSRC, '*.inc'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_opt.h'))
+    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_data.h'))
     return max(os.path.getmtime(p) for p in deps)
 
 

@@ -219,6 +219,28 @@ OPT_SYMBOLS = {
     'qk_lr_schedule_value': (ctypes.c_int, [_LS, ctypes.c_int64, ctypes.c_float, ctypes.POINTER(ctypes.c_float)]),
 }
 
+# ---- include/qk_data.h: the device-resident corpus (a third table, for the same reason) ----
+QK_CORPUS_PLAN_WORDS = 4
+_I64 = ctypes.c_int64
+
+
+class CorpusDesc(ctypes.Structure):
+    """qk_corpus_t (include/qk_data.h)"""
+    _fields_ = [('wave_pack', _VP), ('wave_off', _VP), ('wave_len', _VP), ('label_pack', _VP), ('label_off', _VP), ('label_len', _VP),
+                ('aux_pack', _VP), ('wave_samples', _I64), ('label_words', _I64), ('num_utts', I32), ('reserved', I32)]
+
+
+class BatchScheduleDesc(ctypes.Structure):
+    """qk_batch_schedule_t (include/qk_data.h)"""
+    _fields_ = [('batches', _VP), ('num_batches', I32), ('batch', I32), ('seed', ctypes.c_uint32), ('shuffle', I32)]
+
+
+DATA_SYMBOLS = {
+    'qk_corpus_batch': (ctypes.c_int, [ctypes.POINTER(CorpusDesc), ctypes.POINTER(BatchScheduleDesc), ctypes.c_uint32, _VP, I32, I32,
+                                       _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    'qk_epoch_permutation': (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, I32, ctypes.POINTER(I32)]),
+}
+
 _lib = None
 
 
@@ -231,7 +253,7 @@ def lib():
                 'libqk_hip.so is not built (%s). Run `python -c "import __graft_entry__ as g; '
                 'g.build()"` -- the quaternion layers have no CPU or eager fallback.' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (SYMBOLS, OPT_SYMBOLS):
+        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(handle, name)
                 fn.restype, fn.argtypes = res, args

@@ -2085,3 +2085,104 @@ def noise_reverb(wave, lengths, *, rirs=None, noises=None, rir_prob=1.0, noise_p
                                      _stream(wave))
     L.check(rc, 'qk_noise_reverb')
     return (out, plan) if return_plan else out
+
+
+# ---- Device-resident corpus (include/qk_data.h) ---------------------------------------------------------------------------------
+CorpusArrays = collections.namedtuple('CorpusArrays', 'wave_pack wave_off wave_len label_pack label_off label_len aux_pack')
+CorpusBatch = collections.namedtuple('CorpusBatch', 'wave lengths labels label_length aux utt plan')
+_CORPUS_DTYPES = dict(wave_pack=torch.int16, wave_off=torch.int64, wave_len=torch.int32, label_pack=torch.int32, label_off=torch.int64,
+                      label_len=torch.int32, aux_pack=torch.int32)
+
+
+def _u32_arg(what, name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xFFFFFFFF:
+        raise ValueError('%s: %s must be an integer in [0, 2^32), got %r' % (what, name, v))
+    return int(v)
+
+
+def _corpus_desc(what, corpus):
+    """The checked qk_corpus_t of a CorpusArrays (data.DeviceCorpus.arrays) and the device it lives on."""
+    if not isinstance(corpus, CorpusArrays):
+        raise TypeError('%s: corpus_arrays must be a functional.CorpusArrays (data.DeviceCorpus.arrays), got %r' % (what, type(corpus)))
+    if not torch.is_tensor(corpus.wave_pack) or not corpus.wave_pack.is_cuda:
+        raise RuntimeError('%s: the corpus is not on a GPU. Batches are assembled only on the MI355X HIP path (libqk_hip.so); there '
+                           'is no CPU fallback.' % what)
+    dev = corpus.wave_pack.device
+    for name, dtype in _CORPUS_DTYPES.items():
+        t = getattr(corpus, name)
+        if t is None and name == 'aux_pack':
+            continue
+        if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != dev:
+            raise TypeError('%s: %s must be a contiguous 1-D %s tensor on %s' % (what, name, dtype, dev))
+    num_utts = corpus.wave_len.numel()
+    if num_utts < 1 or any(getattr(corpus, k).numel() != num_utts for k in ('wave_off', 'label_off', 'label_len')):
+        raise ValueError('%s: wave_off, wave_len, label_off and label_len must have one entry per utterance (at least one)' % what)
+    if corpus.wave_pack.numel() < 8 or corpus.wave_pack.numel() % 8 or corpus.wave_pack.data_ptr() % 16:
+        raise ValueError('%s: wave_pack must hold a positive multiple of 8 samples and start on a 16-byte boundary' % what)
+    if corpus.label_pack.numel() < 1 or (corpus.aux_pack is not None and corpus.aux_pack.numel() != corpus.label_pack.numel()):
+        raise ValueError('%s: label_pack must hold at least one word, and aux_pack as many as label_pack' % what)
+    desc = L.CorpusDesc(_ptr(corpus.wave_pack), _ptr(corpus.wave_off), _ptr(corpus.wave_len), _ptr(corpus.label_pack),
+                        _ptr(corpus.label_off), _ptr(corpus.label_len), _ptr(corpus.aux_pack), corpus.wave_pack.numel(),
+                        corpus.label_pack.numel(), num_utts, 0)
+    return desc, dev
+
+
+def corpus_batch(corpus_arrays, batches, position=0, cursor=None, seed=0, shuffle=False, *, n_out, l_out, aux=None, return_utt=False,
+                 return_plan=False):
+    """One batch of a device-resident corpus as one launch (qk_corpus_batch; semantics: include/qk_data.h).
+
+    corpus_arrays: a CorpusArrays of device tensors (data.DeviceCorpus.arrays).  batches: (num_batches, batch) int32 DEVICE matrix of
+    utterance indices; an index outside [0, num_utts) is an empty slot.  The batch is row `perm(seed, epoch, pos)` (shuffle) or
+    `pos` of it, with epoch, pos = divmod(p, num_batches) and p = the value of `cursor` -- a one-element int32 / uint32 DEVICE
+    tensor read by the kernel: advance it with a device op and a captured graph gathers a new batch on every replay -- or, without
+    a cursor, `position`.  n_out / l_out: the widths of the padded waveform and label matrices; longer utterances are CUT (the
+    callers in data.py refuse such widths before they launch).  aux: None = when the corpus has aux words.
+
+    Returns a CorpusBatch: wave (batch, n_out) int16 zero-padded, lengths (batch,) int32, labels (batch, l_out) int32 zero-padded,
+    label_length (batch,) int32, aux (batch, l_out) int32 padded with -1 or None, utt (batch,) int32 (-1: empty slot) or None,
+    plan (4,) int32 = {p, epoch, pos, row} or None.  No host sync."""
+    what = 'corpus_batch'
+    desc, dev = _corpus_desc(what, corpus_arrays)
+    if (not torch.is_tensor(batches) or batches.dtype != torch.int32 or batches.dim() != 2 or min(batches.shape) < 1
+            or not batches.is_contiguous() or batches.device != dev):
+        raise TypeError('%s: batches must be a non-empty contiguous (num_batches, batch) int32 tensor on %s' % (what, dev))
+    position, seed = _u32_arg(what, 'position', position), _u32_arg(what, 'seed', seed)
+    for name, v in (('n_out', n_out), ('l_out', l_out)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError('%s: %s must be an integer >= 1, got %r' % (what, name, v))
+    if cursor is not None:
+        if (not torch.is_tensor(cursor) or cursor.device != dev or cursor.numel() != 1 or cursor.dtype not in (torch.int32, torch.uint32)):
+            raise ValueError('%s: cursor must be a one-element int32 / uint32 tensor on %s' % (what, dev))
+    aux = corpus_arrays.aux_pack is not None if aux is None else bool(aux)
+    if aux and corpus_arrays.aux_pack is None:
+        raise ValueError('%s: aux=True, but the corpus has no aux words' % what)
+    nb, b = batches.shape
+    n_out, l_out = int(n_out), int(l_out)
+    if b * n_out >= 1 << 31 or b * l_out >= 1 << 31:
+        raise ValueError('%s: outputs of 2^31 elements or more are not supported (batch %d, n_out %d, l_out %d)' % (what, b, n_out, l_out))
+    sched = L.BatchScheduleDesc(_ptr(batches), nb, b, seed, int(bool(shuffle)))
+    wave = torch.empty((b, n_out), dtype=torch.int16, device=dev)
+    lengths = torch.empty((b,), dtype=torch.int32, device=dev)
+    labels = torch.empty((b, l_out), dtype=torch.int32, device=dev)
+    label_length = torch.empty((b,), dtype=torch.int32, device=dev)
+    aux_out = torch.empty((b, l_out), dtype=torch.int32, device=dev) if aux else None
+    utt = torch.empty((b,), dtype=torch.int32, device=dev) if return_utt else None
+    plan = torch.empty((L.QK_CORPUS_PLAN_WORDS,), dtype=torch.int32, device=dev) if return_plan else None
+    with _on_device(dev):
+        rc = L.lib().qk_corpus_batch(ctypes.byref(desc), ctypes.byref(sched), position, _ptr(cursor), n_out, l_out, _ptr(wave),
+                                     _ptr(lengths), _ptr(labels), _ptr(label_length), _ptr(aux_out), _ptr(utt), _ptr(plan),
+                                     _stream(wave))
+    L.check(rc, 'qk_corpus_batch')
+    return CorpusBatch(wave, lengths, labels, label_length, aux_out, utt, plan)
+
+
+def epoch_permutation(seed, epoch, num_batches):
+    """The order of one epoch, on the host (qk_epoch_permutation): a (num_batches,) int32 numpy array whose entry `pos` is the row
+    of the schedule that position `pos` of epoch `epoch` reads under `seed`."""
+    seed, epoch = _u32_arg('epoch_permutation', 'seed', seed), _u32_arg('epoch_permutation', 'epoch', epoch)
+    if isinstance(num_batches, bool) or not isinstance(num_batches, (int, np.integer)) or not 1 <= num_batches < 1 << 31:
+        raise ValueError('epoch_permutation: num_batches must be an integer in [1, 2^31), got %r' % (num_batches,))
+    out = np.empty(int(num_batches), dtype=np.int32)
+    L.check(L.lib().qk_epoch_permutation(seed, epoch, int(num_batches), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+            'qk_epoch_permutation')
+    return out
