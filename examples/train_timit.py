@@ -55,6 +55,11 @@ for more than --plateau-patience evaluations (newbob), and every log line shows 
 writes model, optimiser, augmentation counters, step and batch-order state at every evaluation; --resume continues from such a file
 (give the same options; under cosine that includes --steps, which is the schedule's length).  It combines with the guard options above.  No phone error rate has been measured with any of them.
 
+--model qlstm trains qcnn_amd.models.TimitQLSTM in place of the quaternion CNN: --rnn-layers bidirectional QuaternionLSTM layers of
+--rnn-units units (default 4 x 1024) on the same filter-bank input, --dropout between them, the same output layer, loss, decoding
+and evaluation; the frame counts of a batch are the recurrent layers' lengths.  --layers / --filters / --aact do not apply to it.
+No phone error rate has been measured with it.
+
 --device-corpus packs TRAIN and TEST once into device memory (qcnn_amd.data.DeviceCorpus) and takes every training batch from
 DeviceCorpus.next_batch: one launch gathers the padded waveforms, lengths and labels of the next row of an EpochSampler, whose
 order is a keyed permutation of the length-sorted batches evaluated on the device -- real epochs (every batch once per epoch, a new
@@ -242,6 +247,9 @@ def main():
     ap.add_argument('--resume', default=None, metavar='PATH', help='continue from a checkpoint written by --checkpoint')
     ap.add_argument('--device-corpus', action='store_true',
                     help='keep TRAIN and TEST in device memory, shuffle epochs and assemble every batch on the device')
+    ap.add_argument('--model', default='qcnn', choices=['qcnn', 'qlstm'], help='qcnn: the reference model; qlstm: a stack of quaternion LSTM layers')
+    ap.add_argument('--rnn-layers', type=int, default=4, help='qlstm: number of bidirectional QuaternionLSTM layers')
+    ap.add_argument('--rnn-units', type=int, default=1024, help='qlstm: units per direction (a multiple of 64 runs on the matrix cores)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
@@ -284,7 +292,12 @@ def main():
                               l2=args.l2, model='quaternion', quat_init='quaternion')
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
-    model, _ = getTimitModel2D(d)
+    if args.model == 'qlstm':
+        from qcnn_amd.models import TimitQLSTM
+        model = TimitQLSTM(num_layers=args.rnn_layers, units=args.rnn_units, bidirectional=True, dropout=args.dropout, l2=args.l2)
+        print('model: %d bidirectional quaternion LSTM layers of %d units' % (args.rnn_layers, args.rnn_units))
+    else:
+        model, _ = getTimitModel2D(d)
     x0 = (to_device(train, batches[0][:1], dev, dtype) if corpus is None else device_batch(corpus.batch(batches[0][:1]), dtype))[0]
     with torch.no_grad():
         model(x0)                                                 # build-on-first-call, like Keras

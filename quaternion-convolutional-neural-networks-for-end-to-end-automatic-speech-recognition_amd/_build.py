@@ -21,6 +21,7 @@ def _newest_header():
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_opt.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_data.h'))
+    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_rnn.h'))
     return max(os.path.getmtime(p) for p in deps)
 
 

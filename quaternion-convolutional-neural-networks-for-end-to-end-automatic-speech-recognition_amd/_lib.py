@@ -241,6 +241,27 @@ DATA_SYMBOLS = {
     'qk_epoch_permutation': (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, I32, ctypes.POINTER(I32)]),
 }
 
+# ---- include/qk_rnn.h: the quaternion LSTM recurrence (a fourth table, for the same reason) ----
+QK_QLSTM_REVERSE = 1
+QK_QLSTM_PATH_GENERIC, QK_QLSTM_PATH_MFMA16 = 1, 2
+QK_QLSTM_PATH_NAMES = {0: 'none', QK_QLSTM_PATH_GENERIC: 'generic', QK_QLSTM_PATH_MFMA16: 'mfma16'}
+
+
+class QLSTMDesc(ctypes.Structure):
+    """qk_qlstm_desc_t (include/qk_rnn.h)"""
+    _fields_ = [('dtype', I32), ('batch', I32), ('steps', I32), ('q_units', I32), ('directions', I32), ('y_stride', I32), ('flags', I32)]
+
+
+_QD = ctypes.POINTER(QLSTMDesc)
+
+RNN_SYMBOLS = {
+    'qk_qlstm_supported': (ctypes.c_int, [_QD]),
+    'qk_qlstm_workspace_bytes': (_SZ, [_QD, I32]),
+    'qk_qlstm_reserve_bytes': (_SZ, [_QD]),
+    'qk_qlstm_fwd': (ctypes.c_int, [_QD, _VP, _FP, _VP, _VP, _FP, _VP, _VP, _FP, _VP, _VP, _SZ, _VP]),
+    'qk_qlstm_bwd': (ctypes.c_int, [_QD, _VP, _VP, _FP, _FP, _VP, _VP, _FP, _VP, _VP, _VP, _VP, _VP, _FP, _VP, _SZ, _VP]),
+}
+
 _lib = None
 
 
@@ -253,7 +274,7 @@ def lib():
                 'libqk_hip.so is not built (%s). Run `python -c "import __graft_entry__ as g; '
                 'g.build()"` -- the quaternion layers have no CPU or eager fallback.' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS):
+        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS, RNN_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(handle, name)
                 fn.restype, fn.argtypes = res, args

@@ -2186,3 +2186,124 @@ def epoch_permutation(seed, epoch, num_batches):
     L.check(L.lib().qk_epoch_permutation(seed, epoch, int(num_batches), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
             'qk_epoch_permutation')
     return out
+
+
+# ---- include/qk_rnn.h: the quaternion LSTM recurrence ----------------------------------------------------------------------------
+def _aligned16(t):
+    """t (or None) contiguous and 16-byte aligned: the recurrent kernels read 16-byte fragments."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def qlstm_desc(dtype, batch, steps, q_units, directions, reverse=False):
+    return L.QLSTMDesc(_DTYPES[dtype], int(batch), int(steps), int(q_units), int(directions), int(directions) * 4 * int(q_units),
+                       L.QK_QLSTM_REVERSE if reverse else 0)
+
+
+def qlstm_path(dtype, batch, steps, q_units, directions=1):
+    """'mfma16' / 'generic': the kernel family qk_qlstm_fwd / qk_qlstm_bwd run for this shape (qk_qlstm_supported)."""
+    desc = qlstm_desc(dtype, batch, steps, q_units, directions)
+    path = L.lib().qk_qlstm_supported(ctypes.byref(desc))
+    if path == 0:
+        L.check(L.QK_ERR_INVALID_ARG, 'qk_qlstm_supported')
+    return L.QK_QLSTM_PATH_NAMES[path]
+
+
+class _QLSTMFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, zx, R, lengths, h0, c0, reverse):
+        D, B, T, G = zx.shape
+        U = G // 4
+        desc = qlstm_desc(zx.dtype, B, T, U // 4, D, reverse)
+        dev = zx.device
+        y = torch.empty((B, T, D * U), dtype=zx.dtype, device=dev)
+        hT = torch.empty((D, B, U), dtype=zx.dtype, device=dev)
+        cT = torch.empty((D, B, U), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            lib = L.lib()
+            n = int(lib.qk_qlstm_workspace_bytes(ctypes.byref(desc), L.QK_OP_FWD))
+            nr = int(lib.qk_qlstm_reserve_bytes(ctypes.byref(desc)))
+            if n == 0 or nr == 0:
+                L.check(L.QK_ERR_INVALID_ARG, 'qk_qlstm_workspace_bytes')
+            ws = torch.empty(n, dtype=torch.uint8, device=dev)
+            reserve = torch.empty(nr, dtype=torch.uint8, device=dev)
+            rc = lib.qk_qlstm_fwd(ctypes.byref(desc), _ptr(zx), _ptr(R), _ptr(lengths), _ptr(h0), _ptr(c0), _ptr(y), _ptr(hT), _ptr(cT),
+                                  _ptr(reserve), _ptr(ws), n, _stream(zx))
+        L.check(rc, 'qk_qlstm_fwd')
+        ctx.desc, ctx.shape = desc, (D, B, T, U)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(R, lengths, h0, c0, y, reserve)
+        return y, hT, cT
+
+    @staticmethod
+    def backward(ctx, dy, dhT, dcT):
+        R, lengths, h0, c0, y, reserve = ctx.saved_tensors
+        desc, (D, B, T, U) = ctx.desc, ctx.shape
+        dev, dtype = y.device, y.dtype
+        dy = _aligned16(dy) if dy is not None else torch.zeros((B, T, D * U), dtype=dtype, device=dev)
+        dhT = _aligned16(dhT)
+        dcT = dcT.contiguous() if dcT is not None else None
+        dzx = torch.empty((D, B, T, 4 * U), dtype=dtype, device=dev)
+        hprev = torch.empty((D, B, T, U), dtype=dtype, device=dev)
+        dh0 = torch.empty((D, B, U), dtype=dtype, device=dev)
+        dc0 = torch.empty((D, B, U), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            lib = L.lib()
+            n = int(lib.qk_qlstm_workspace_bytes(ctypes.byref(desc), L.QK_OP_BWD))
+            ws = torch.empty(n, dtype=torch.uint8, device=dev)
+            rc = lib.qk_qlstm_bwd(ctypes.byref(desc), _ptr(dy), _ptr(dhT), _ptr(dcT), _ptr(R), _ptr(lengths), _ptr(h0), _ptr(c0), _ptr(y),
+                                  _ptr(reserve), _ptr(dzx), _ptr(hprev), _ptr(dh0), _ptr(dc0), _ptr(ws), n, _stream(dy))
+        L.check(rc, 'qk_qlstm_bwd')
+        dR = None
+        if ctx.needs_input_grad[1]:
+            # dR[d] = sum_t dense-weight-gradient(h_{t-1}, dz_t): ONE dense backward-weight over the stacked (B * T) rows per direction
+            # (inactive rows hold dz = 0)
+            call = dense_call((B * T, U), (U // 4, 4 * U), dtype, None, False)
+            dR = torch.empty((D, U // 4, 4 * U), dtype=torch.float32, device=dev)
+            for d in range(D):
+                call.bwd_weight(hprev[d].view(B * T, U), dzx[d].view(B * T, 4 * U), None, False, out=(dR[d], None))
+        return (dzx, dR, None, dh0 if ctx.needs_input_grad[3] else None, dc0 if ctx.needs_input_grad[4] else None, None)
+
+
+def qlstm(zx, R, lengths=None, h0=None, c0=None, reverse=False):
+    """The quaternion LSTM recurrence (include/qk_rnn.h): one launch per time step, both directions in each.
+
+    zx       (D, B, T, 4 * units): the input projection quaternion_dense(x, W) + b of each direction, D = 1 or 2 -- or (B, T, 4 * units)
+             for one direction, with R (q_units, 4 * units) and states (B, units)
+    R        (D, q_units, 4 * units) float32: the recurrent weight, a QuaternionDense weight of 4 * units outputs (gates i|f|g|o)
+    lengths  (B,) int32 or None: rows are inactive from t = lengths[b] on (state carried, y = 0, no gradient)
+    h0, c0   (D, B, units) or None (zero): h0 in zx's dtype, c0 float32
+    reverse  one direction only: walk t = T-1 .. 0 (direction 1 of a two-direction call always does)
+
+    Returns (y, hT, cT): y (B, T, D * units) in zx's dtype -- component c, direction d, unit u at column c * (D * q_units) + d * q_units
+    + u -- hT (D, B, units) in zx's dtype, cT (D, B, units) float32.  The backward returns dzx, dR, dh0, dc0."""
+    _require_device(zx, 'qlstm')
+    single = zx.dim() == 3
+    if single:
+        zx, R = zx.unsqueeze(0), R.unsqueeze(0)
+        h0 = h0.unsqueeze(0) if h0 is not None else None
+        c0 = c0.unsqueeze(0) if c0 is not None else None
+    if zx.dim() != 4 or R.dim() != 3 or zx.shape[0] not in (1, 2) or zx.shape[-1] % 16:
+        raise ValueError('qlstm: zx must be (D, B, T, 4 * units) with D in (1, 2) and units divisible by 4, got %s' % (tuple(zx.shape),))
+    D, B, T, G = zx.shape
+    U = G // 4
+    if R.dtype != torch.float32 or tuple(R.shape) != (D, U // 4, 4 * U):
+        raise ValueError('qlstm: R must be float32 of shape %s, got %s %s' % ((D, U // 4, 4 * U), R.dtype, tuple(R.shape)))
+    if reverse and D != 1:
+        raise ValueError('qlstm: reverse needs one direction')
+    if B == 0 or T == 0:
+        raise ValueError('qlstm: empty batch or sequence')
+    if lengths is not None:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or lengths.device != zx.device:
+            raise ValueError('qlstm: lengths must be an int32 tensor of shape (%d,) on %s' % (B, zx.device))
+        lengths = lengths.contiguous()
+    for name, s, dt in (('h0', h0, zx.dtype), ('c0', c0, torch.float32)):
+        if s is not None and (tuple(s.shape) != (D, B, U) or s.dtype != dt or s.device != zx.device):
+            raise ValueError('qlstm: %s must be %s of shape %s on %s' % (name, dt, (D, B, U), zx.device))
+    y, hT, cT = _QLSTMFn.apply(_aligned16(zx), R.contiguous(), lengths, _aligned16(h0), c0.contiguous() if c0 is not None else None,
+                               bool(reverse))
+    if single:
+        hT, cT = hT[0], cT[0]
+    return y, hT, cT

@@ -2,3 +2,4 @@
 models/interspeech_model.py): callers of the quaternion hot path, kept as thin torch modules."""
 from .example_model import CNN, DNN
 from .interspeech_model import getTimitModel2D, TimitQCNN
+from .qlstm_model import TimitQLSTM
