@@ -58,6 +58,7 @@ writes model, optimiser, augmentation counters, step and batch-order state at ev
 --model qlstm trains qcnn_amd.models.TimitQLSTM in place of the quaternion CNN: --rnn-layers bidirectional QuaternionLSTM layers of
 --rnn-units units (default 4 x 1024) on the same filter-bank input, --dropout between them, the same output layer, loss, decoding
 and evaluation; the frame counts of a batch are the recurrent layers' lengths.  --layers / --filters / --aact do not apply to it.
+--layer-norm puts a quaternion layer normalisation (qcnn_amd.complexnn.QuaternionLayerNormalization) behind every recurrent layer.
 No phone error rate has been measured with it.
 
 --device-corpus packs TRAIN and TEST once into device memory (qcnn_amd.data.DeviceCorpus) and takes every training batch from
@@ -250,7 +251,10 @@ def main():
     ap.add_argument('--model', default='qcnn', choices=['qcnn', 'qlstm'], help='qcnn: the reference model; qlstm: a stack of quaternion LSTM layers')
     ap.add_argument('--rnn-layers', type=int, default=4, help='qlstm: number of bidirectional QuaternionLSTM layers')
     ap.add_argument('--rnn-units', type=int, default=1024, help='qlstm: units per direction (a multiple of 64 runs on the matrix cores)')
+    ap.add_argument('--layer-norm', action='store_true', help='qlstm: a quaternion layer normalisation behind every recurrent layer')
     args = ap.parse_args()
+    if args.layer_norm and args.model != 'qlstm':
+        ap.error('--layer-norm needs --model qlstm')
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
     dtype = getattr(torch, args.dtype)
@@ -294,8 +298,10 @@ def main():
     torch.manual_seed(args.seed)
     if args.model == 'qlstm':
         from qcnn_amd.models import TimitQLSTM
-        model = TimitQLSTM(num_layers=args.rnn_layers, units=args.rnn_units, bidirectional=True, dropout=args.dropout, l2=args.l2)
-        print('model: %d bidirectional quaternion LSTM layers of %d units' % (args.rnn_layers, args.rnn_units))
+        model = TimitQLSTM(num_layers=args.rnn_layers, units=args.rnn_units, bidirectional=True, dropout=args.dropout, l2=args.l2,
+                           layer_norm=args.layer_norm)
+        print('model: %d bidirectional quaternion LSTM layers of %d units%s' % (args.rnn_layers, args.rnn_units,
+                                                                                ', layer normalisation' if args.layer_norm else ''))
     else:
         model, _ = getTimitModel2D(d)
     x0 = (to_device(train, batches[0][:1], dev, dtype) if corpus is None else device_batch(corpus.batch(batches[0][:1]), dtype))[0]

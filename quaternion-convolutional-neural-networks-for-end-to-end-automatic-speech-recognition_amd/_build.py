@@ -22,6 +22,7 @@ def _newest_header():
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_opt.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_data.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_rnn.h'))
+    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_norm.h'))
     return max(os.path.getmtime(p) for p in deps)
 
 

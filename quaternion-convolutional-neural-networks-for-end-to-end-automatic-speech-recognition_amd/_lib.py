@@ -262,6 +262,26 @@ RNN_SYMBOLS = {
     'qk_qlstm_bwd': (ctypes.c_int, [_QD, _VP, _VP, _FP, _FP, _VP, _VP, _FP, _VP, _VP, _VP, _VP, _VP, _FP, _VP, _SZ, _VP]),
 }
 
+# ---- include/qk_norm.h: quaternion layer normalisation (a fifth table, for the same reason) ----
+QK_QLNORM_PATH_GENERIC, QK_QLNORM_PATH_VEC = 1, 2
+QK_QLNORM_PATH_NAMES = {0: 'none', QK_QLNORM_PATH_GENERIC: 'generic', QK_QLNORM_PATH_VEC: 'vec'}
+
+
+class QLNormDesc(ctypes.Structure):
+    """qk_qlnorm_desc_t (include/qk_norm.h)"""
+    _fields_ = [('dtype', I32), ('rows', I32), ('steps', I32), ('q', I32), ('x_stride', I32), ('y_stride', I32), ('flags', I32)]
+
+
+_ND = ctypes.POINTER(QLNormDesc)
+
+NORM_SYMBOLS = {
+    'qk_qlnorm_supported': (ctypes.c_int, [_ND]),
+    'qk_qlnorm_slab_rows': (ctypes.c_int, [_ND]),
+    'qk_qlnorm_workspace_bytes': (_SZ, [_ND, I32]),
+    'qk_qlnorm_fwd': (ctypes.c_int, [_ND, _VP, _FP, _FP, _VP, ctypes.c_float, _VP, _FP, _VP]),
+    'qk_qlnorm_bwd': (ctypes.c_int, [_ND, _VP, _VP, _FP, _VP, _FP, _VP, _FP, _FP, _VP, _SZ, _VP]),
+}
+
 _lib = None
 
 
@@ -274,7 +294,7 @@ def lib():
                 'libqk_hip.so is not built (%s). Run `python -c "import __graft_entry__ as g; '
                 'g.build()"` -- the quaternion layers have no CPU or eager fallback.' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS, RNN_SYMBOLS):
+        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS, RNN_SYMBOLS, NORM_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(handle, name)
                 fn.restype, fn.argtypes = res, args

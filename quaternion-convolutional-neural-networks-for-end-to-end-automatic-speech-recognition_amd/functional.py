@@ -2307,3 +2307,95 @@ def qlstm(zx, R, lengths=None, h0=None, c0=None, reverse=False):
     if single:
         hT, cT = hT[0], cT[0]
     return y, hT, cT
+
+
+# ---- include/qk_norm.h: quaternion layer normalisation ---------------------------------------------------------------------------
+def qlayer_norm_desc(dtype, rows, q, steps=0, x_stride=None, y_stride=None):
+    """qk_qlnorm_desc_t for `rows` rows of 4 * q columns; strides in elements (default: dense rows)."""
+    width = 4 * int(q)
+    return L.QLNormDesc(_DTYPES[dtype], int(rows), int(steps), int(q), width if x_stride is None else int(x_stride),
+                        width if y_stride is None else int(y_stride), 0)
+
+
+def qlayer_norm_path(dtype, rows, q):
+    """'vec' / 'generic': the kernel family qk_qlnorm_fwd / qk_qlnorm_bwd run for dense, 16-byte aligned rows of this shape
+    (qk_qlnorm_supported)."""
+    desc = qlayer_norm_desc(dtype, rows, q)
+    path = L.lib().qk_qlnorm_supported(ctypes.byref(desc))
+    if path == 0:
+        L.check(L.QK_ERR_INVALID_ARG, 'qk_qlnorm_supported')
+    return L.QK_QLNORM_PATH_NAMES[path]
+
+
+def _rows_of(t, width):
+    """t (N, width) as the kernels take it: unit column stride and a row stride >= width (a column window stays a view)."""
+    return t if t.stride(1) == 1 and (t.stride(0) >= width or t.shape[0] == 1) and t.stride(0) < 2 ** 31 else t.contiguous()
+
+
+class _QLNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, lengths, steps, epsilon):
+        N, W = x.shape
+        x = _rows_of(x, W)
+        desc = qlayer_norm_desc(x.dtype, N, W // 4, steps, max(x.stride(0), W), W)
+        dev = x.device
+        y = torch.empty((N, W), dtype=x.dtype, device=dev)
+        stats = torch.empty((N, 5), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            rc = L.lib().qk_qlnorm_fwd(ctypes.byref(desc), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(lengths), float(epsilon), _ptr(y),
+                                       _ptr(stats), _stream(x))
+        L.check(rc, 'qk_qlnorm_fwd')
+        ctx.steps = steps
+        ctx.save_for_backward(x, gamma, lengths, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, lengths, stats = ctx.saved_tensors
+        N, W = x.shape
+        dev = x.device
+        if x.stride(0) != W and N > 1:
+            x = x.contiguous()                      # dx has x's row stride: a column window is gathered once here
+        dy = _rows_of(dy, W)
+        desc = qlayer_norm_desc(x.dtype, N, W // 4, ctx.steps, W, max(dy.stride(0), W))
+        dx = torch.empty((N, W), dtype=x.dtype, device=dev)
+        dgamma = torch.empty((W // 4,), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        dbeta = torch.empty((W,), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        with _on_device(dev):
+            lib = L.lib()
+            n, ws = 0, None
+            if dgamma is not None or dbeta is not None:
+                n = int(lib.qk_qlnorm_workspace_bytes(ctypes.byref(desc), L.QK_OP_BWD))
+                if n == 0:
+                    L.check(L.QK_ERR_INVALID_ARG, 'qk_qlnorm_workspace_bytes')
+                ws = torch.empty(n, dtype=torch.uint8, device=dev)
+            rc = lib.qk_qlnorm_bwd(ctypes.byref(desc), _ptr(dy), _ptr(x), _ptr(gamma), _ptr(lengths), _ptr(stats), _ptr(dx), _ptr(dgamma),
+                                   _ptr(dbeta), _ptr(ws), n, _stream(x))
+        L.check(rc, 'qk_qlnorm_bwd')
+        return dx, dgamma, dbeta, None, None, None
+
+
+def qlayer_norm(x, gamma=None, beta=None, lengths=None, epsilon=1e-3):
+    """Quaternion layer normalisation (include/qk_norm.h) of the last axis of x, (..., 4 Q) component-major r|i|j|k: per row the four
+    component means are removed and ONE variance over all 4 Q values scales the row.
+
+    gamma    (Q,) float32 or None: one scale per quaternion unit, shared by its four components
+    beta     (4 Q,) float32 or None
+    lengths  (B,) int32 or None, with x (B, T, 4 Q): rows with t >= lengths[b] are inactive -- y = 0 (not beta), no gradient
+    Returns y in x's shape and dtype; the backward returns dx, dgamma, dbeta."""
+    _require_device(x, 'qlayer_norm')
+    if x.dim() < 1 or x.shape[-1] % 4 or x.numel() == 0:
+        raise ValueError('qlayer_norm: x must be a non-empty (..., 4 Q) tensor, got %s' % (tuple(x.shape),))
+    W = x.shape[-1]
+    steps = 0
+    if lengths is not None:
+        if x.dim() != 3:
+            raise ValueError('qlayer_norm: lengths needs x of shape (B, T, 4 Q), got %s' % (tuple(x.shape),))
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (x.shape[0],) or lengths.device != x.device:
+            raise ValueError('qlayer_norm: lengths must be an int32 tensor of shape (%d,) on %s' % (x.shape[0], x.device))
+        lengths, steps = lengths.contiguous(), x.shape[1]
+    for name, p, n in (('gamma', gamma, W // 4), ('beta', beta, W)):
+        if p is not None and (p.dtype != torch.float32 or tuple(p.shape) != (n,) or p.device != x.device):
+            raise ValueError('qlayer_norm: %s must be float32 of shape (%d,) on %s' % (name, n, x.device))
+    y = _QLNormFn.apply(x.reshape(-1, W), _aligned16(gamma), _aligned16(beta), lengths, steps, float(epsilon))
+    return y.view(x.shape)

@@ -4,7 +4,7 @@ of the convolutions and TimeDistributed dense layers.  The reference has no such
 with it."""
 import torch
 
-from ..complexnn import QuaternionLSTM
+from ..complexnn import QuaternionLayerNormalization, QuaternionLSTM
 from ..keras_like import regularizers
 from ..layers import Dense, Dropout, TimeDistributed, ctc_batch_cost, dense_softmax_ctc_mean
 from .interspeech_model import TimitQCNN
@@ -14,18 +14,23 @@ class TimitQLSTM(TimitQCNN):
     """x (B, 4, F, T) -- the quaternion filter-bank input of TimitQCNN (F = 41: 40 filters + energy; r = 0, i / j / k = static,
     delta, delta-delta) -- is viewed as (B, T, 4 * F): component-major r|i|j|k, as every quaternion layer here reads its input.
     `num_layers` QuaternionLSTM(units) layers follow, Dropout between them, then TimeDistributed(Dense(62, softmax)).
+    layer_norm=True puts one QuaternionLayerNormalization behind every recurrent layer (`self.norm`), in front of the next layer's
+    dropout and with the same `lengths`; without it no such module, parameter or state_dict key exists.
 
     The decoding / scoring surface (ctc_loss, ctc_mean_loss, decode, evaluate, error_breakdown, align, transcribe,
     regularization_loss, training_loss) is TimitQCNN's; `input_length` is also handed to the recurrent layers as `lengths`, so
     that padding frames neither move the state nor, in the backward direction, come before an utterance's last frame."""
 
-    def __init__(self, num_layers=4, units=1024, bidirectional=True, dropout=0.2, l2=0.0):
+    def __init__(self, num_layers=4, units=1024, bidirectional=True, dropout=0.2, l2=0.0, layer_norm=False):
         torch.nn.Module.__init__(self)
         reg = regularizers.l2(l2) if l2 else None
         self.rate = dropout
         self.rnn = torch.nn.ModuleList([QuaternionLSTM(units, bidirectional=bidirectional, kernel_regularizer=reg,
                                                        recurrent_regularizer=reg, seed=1337 + 16 * i, name='qlstm%d' % i)
                                         for i in range(num_layers)])
+        self.layer_norm = bool(layer_norm)
+        if self.layer_norm:
+            self.norm = torch.nn.ModuleList([QuaternionLayerNormalization(name='qlnorm%d' % i) for i in range(num_layers)])
         self.drop = Dropout(dropout)
         self.pred = TimeDistributed(Dense(62, activation='softmax', kernel_regularizer=reg, use_bias=True,
                                           bias_initializer='zeros', kernel_initializer='random_uniform'))
@@ -44,6 +49,8 @@ class TimitQLSTM(TimitQCNN):
             if i:
                 o = self.drop(o)
             o = layer(o, lengths=lengths)
+            if self.layer_norm:
+                o = self.norm[i](o, lengths=lengths)
         return o
 
     def forward(self, x, input_length=None):
