@@ -61,6 +61,13 @@ and evaluation; the frame counts of a batch are the recurrent layers' lengths.  
 --layer-norm puts a quaternion layer normalisation (qcnn_amd.complexnn.QuaternionLayerNormalization) behind every recurrent layer.
 No phone error rate has been measured with it.
 
+--model qtransformer trains qcnn_amd.models.TimitQTransformer: a QuaternionDense projection to --tf-units plus a fixed sinusoidal
+position table, --tf-layers pre-norm encoder blocks (quaternion layer normalisation, QuaternionMultiHeadAttention with --tf-heads
+heads, a feed-forward pair of QuaternionDense layers --tf-ff wide; --dropout in both residual branches), a final normalisation and
+the same output layer, loss, decoding and evaluation; the frame counts of a batch are the attention's lengths, so padding frames
+are never attended to.  --tf-units = 64 or 128 times --tf-heads runs the attention on the matrix cores in bf16 / fp16.
+No phone error rate has been measured with it.
+
 --device-corpus packs TRAIN and TEST once into device memory (qcnn_amd.data.DeviceCorpus) and takes every training batch from
 DeviceCorpus.next_batch: one launch gathers the padded waveforms, lengths and labels of the next row of an EpochSampler, whose
 order is a keyed permutation of the length-sorted batches evaluated on the device -- real epochs (every batch once per epoch, a new
@@ -248,10 +255,15 @@ def main():
     ap.add_argument('--resume', default=None, metavar='PATH', help='continue from a checkpoint written by --checkpoint')
     ap.add_argument('--device-corpus', action='store_true',
                     help='keep TRAIN and TEST in device memory, shuffle epochs and assemble every batch on the device')
-    ap.add_argument('--model', default='qcnn', choices=['qcnn', 'qlstm'], help='qcnn: the reference model; qlstm: a stack of quaternion LSTM layers')
+    ap.add_argument('--model', default='qcnn', choices=['qcnn', 'qlstm', 'qtransformer'],
+                    help='qcnn: the reference model; qlstm: a stack of quaternion LSTM layers; qtransformer: quaternion self-attention encoder blocks')
     ap.add_argument('--rnn-layers', type=int, default=4, help='qlstm: number of bidirectional QuaternionLSTM layers')
     ap.add_argument('--rnn-units', type=int, default=1024, help='qlstm: units per direction (a multiple of 64 runs on the matrix cores)')
     ap.add_argument('--layer-norm', action='store_true', help='qlstm: a quaternion layer normalisation behind every recurrent layer')
+    ap.add_argument('--tf-layers', type=int, default=6, help='qtransformer: number of encoder blocks')
+    ap.add_argument('--tf-units', type=int, default=512, help='qtransformer: model width (64 or 128 per head runs the attention on the matrix cores)')
+    ap.add_argument('--tf-heads', type=int, default=8, help='qtransformer: attention heads (must divide tf-units / 4)')
+    ap.add_argument('--tf-ff', type=int, default=2048, help='qtransformer: width of the feed-forward layer')
     args = ap.parse_args()
     if args.layer_norm and args.model != 'qlstm':
         ap.error('--layer-norm needs --model qlstm')
@@ -302,6 +314,12 @@ def main():
                            layer_norm=args.layer_norm)
         print('model: %d bidirectional quaternion LSTM layers of %d units%s' % (args.rnn_layers, args.rnn_units,
                                                                                 ', layer normalisation' if args.layer_norm else ''))
+    elif args.model == 'qtransformer':
+        from qcnn_amd.models import TimitQTransformer
+        model = TimitQTransformer(num_layers=args.tf_layers, units=args.tf_units, heads=args.tf_heads, ff_units=args.tf_ff, dropout=args.dropout,
+                                  l2=args.l2)
+        print('model: %d quaternion transformer encoder blocks of %d units, %d heads, feed-forward %d'
+              % (args.tf_layers, args.tf_units, args.tf_heads, args.tf_ff))
     else:
         model, _ = getTimitModel2D(d)
     x0 = (to_device(train, batches[0][:1], dev, dtype) if corpus is None else device_batch(corpus.batch(batches[0][:1]), dtype))[0]

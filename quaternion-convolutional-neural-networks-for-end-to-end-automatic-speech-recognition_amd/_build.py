@@ -23,6 +23,7 @@ def _newest_header():
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_data.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_rnn.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_norm.h'))
+    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_attn.h'))
     return max(os.path.getmtime(p) for p in deps)
 
 

@@ -282,6 +282,26 @@ NORM_SYMBOLS = {
     'qk_qlnorm_bwd': (ctypes.c_int, [_ND, _VP, _VP, _FP, _VP, _FP, _VP, _FP, _FP, _VP, _SZ, _VP]),
 }
 
+# ---- include/qk_attn.h: quaternion multi-head self-attention (a sixth table, for the same reason) ----
+QK_QATTN_PATH_GENERIC, QK_QATTN_PATH_MFMA = 1, 2
+QK_QATTN_PATH_NAMES = {0: 'none', QK_QATTN_PATH_GENERIC: 'generic', QK_QATTN_PATH_MFMA: 'mfma'}
+
+
+class QAttnDesc(ctypes.Structure):
+    """qk_qattn_desc_t (include/qk_attn.h)"""
+    _fields_ = [('dtype', I32), ('batch', I32), ('steps', I32), ('heads', I32), ('dq', I32), ('q_row', I32), ('q_comp', I32),
+                ('k_row', I32), ('k_comp', I32), ('v_row', I32), ('v_comp', I32), ('o_row', I32), ('o_comp', I32), ('flags', I32)]
+
+
+_AD = ctypes.POINTER(QAttnDesc)
+
+ATTN_SYMBOLS = {
+    'qk_qattn_supported': (ctypes.c_int, [_AD]),
+    'qk_qattn_workspace_bytes': (_SZ, [_AD, I32]),
+    'qk_qattn_fwd': (ctypes.c_int, [_AD, _VP, _VP, _VP, _VP, ctypes.c_float, _VP, _FP, _VP]),
+    'qk_qattn_bwd': (ctypes.c_int, [_AD, _VP, _VP, _VP, _VP, _VP, _FP, _VP, ctypes.c_float, _VP, _VP, _VP, _VP, _SZ, _VP]),
+}
+
 _lib = None
 
 
@@ -294,7 +314,7 @@ def lib():
                 'libqk_hip.so is not built (%s). Run `python -c "import __graft_entry__ as g; '
                 'g.build()"` -- the quaternion layers have no CPU or eager fallback.' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS, RNN_SYMBOLS, NORM_SYMBOLS):
+        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS, RNN_SYMBOLS, NORM_SYMBOLS, ATTN_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(handle, name)
                 fn.restype, fn.argtypes = res, args

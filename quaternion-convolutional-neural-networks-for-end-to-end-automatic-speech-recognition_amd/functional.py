@@ -2399,3 +2399,148 @@ def qlayer_norm(x, gamma=None, beta=None, lengths=None, epsilon=1e-3):
             raise ValueError('qlayer_norm: %s must be float32 of shape (%d,) on %s' % (name, n, x.device))
     y = _QLNormFn.apply(x.reshape(-1, W), _aligned16(gamma), _aligned16(beta), lengths, steps, float(epsilon))
     return y.view(x.shape)
+
+
+# ---- include/qk_attn.h: quaternion multi-head self-attention --------------------------------------------------------------------
+def qattention_desc(dtype, batch, steps, heads, dq, q=None, k=None, v=None, o=None):
+    """qk_qattn_desc_t for (batch, steps, 4 * heads * dq) tensors; q, k, v, o are (row, comp) stride pairs in elements (default: dense
+    rows of 4 Q columns, components Q apart)."""
+    Q = int(heads) * int(dq)
+    pairs = [(4 * Q, Q) if s is None else (int(s[0]), int(s[1])) for s in (q, k, v, o)]
+    return L.QAttnDesc(_DTYPES[dtype], int(batch), int(steps), int(heads), int(dq), pairs[0][0], pairs[0][1], pairs[1][0], pairs[1][1],
+                       pairs[2][0], pairs[2][1], pairs[3][0], pairs[3][1], 0)
+
+
+def qattention_path(dtype, batch, steps, heads, dq, packed=False):
+    """'mfma' / 'generic': the kernel family qk_qattn_fwd / qk_qattn_bwd run for dense (packed: (B, T, 12 Q)), 16-byte aligned tensors
+    of this shape (qk_qattn_supported)."""
+    Q = int(heads) * int(dq)
+    s = (12 * Q, 3 * Q) if packed else None
+    desc = qattention_desc(dtype, batch, steps, heads, dq, s, s, s, None)
+    path = L.lib().qk_qattn_supported(ctypes.byref(desc))
+    if path == 0:
+        L.check(L.QK_ERR_INVALID_ARG, 'qk_qattn_supported')
+    return L.QK_QATTN_PATH_NAMES[path]
+
+
+def _attn_rows(t, width):
+    """t (B, T, width) as the attention kernels address it -- row b * T + t at (b * T + t) * row, unit column stride -- and its row
+    stride in elements; a column window of a wider (B, T, W) buffer stays a view."""
+    B, T, _ = t.shape
+    row = t.stride(1) if T > 1 else (t.stride(0) if B > 1 else width)
+    if t.stride(2) == 1 and width <= row < 2 ** 30 and (B == 1 or T == 1 or t.stride(0) == T * row):
+        return t, row
+    return t.contiguous(), width
+
+
+def _qattn_fwd(dtype, B, T, heads, dq, strides, ptrs, lengths, scale, dev, stream_of):
+    Q = heads * dq
+    desc = qattention_desc(dtype, B, T, heads, dq, strides[0], strides[1], strides[2], None)
+    o = torch.empty((B, T, 4 * Q), dtype=dtype, device=dev)
+    lse = torch.empty((B, heads, T), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = L.lib().qk_qattn_fwd(ctypes.byref(desc), ptrs[0], ptrs[1], ptrs[2], _ptr(lengths), float(scale), _ptr(o), _ptr(lse),
+                                  _stream(stream_of))
+    L.check(rc, 'qk_qattn_fwd')
+    return o, lse
+
+
+def _qattn_bwd(dtype, B, T, heads, dq, strides, ptrs, gptrs, do, o, lse, lengths, scale, dev):
+    desc = qattention_desc(dtype, B, T, heads, dq, strides[0], strides[1], strides[2], None)
+    with _on_device(dev):
+        lib = L.lib()
+        n = int(lib.qk_qattn_workspace_bytes(ctypes.byref(desc), L.QK_OP_BWD))
+        if n == 0:
+            L.check(L.QK_ERR_INVALID_ARG, 'qk_qattn_workspace_bytes')
+        ws = torch.empty(n, dtype=torch.uint8, device=dev)
+        rc = lib.qk_qattn_bwd(ctypes.byref(desc), _ptr(do), ptrs[0], ptrs[1], ptrs[2], _ptr(o), _ptr(lse), _ptr(lengths), float(scale),
+                              gptrs[0], gptrs[1], gptrs[2], _ptr(ws), n, _stream(do))
+    L.check(rc, 'qk_qattn_bwd')
+
+
+class _QAttnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, lengths, heads, scale):
+        B, T, W = q.shape
+        Q = W // 4
+        views = [_attn_rows(t, W) for t in (q, k, v)]
+        o, lse = _qattn_fwd(q.dtype, B, T, heads, Q // heads, [(r, Q) for _, r in views], [t.data_ptr() for t, _ in views], lengths,
+                            scale, q.device, q)
+        ctx.heads, ctx.scale = heads, scale
+        ctx.save_for_backward(views[0][0], views[1][0], views[2][0], o, lse, lengths)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, lengths = ctx.saved_tensors
+        B, T, W = o.shape
+        Q = W // 4
+        q, k, v, do = q.contiguous(), k.contiguous(), v.contiguous(), do.contiguous()      # the gradients are dense: so are their inputs
+        grads = [torch.empty((B, T, W), dtype=o.dtype, device=o.device) for _ in range(3)]
+        _qattn_bwd(o.dtype, B, T, ctx.heads, Q // ctx.heads, [(W, Q)] * 3, [q.data_ptr(), k.data_ptr(), v.data_ptr()],
+                   [g.data_ptr() for g in grads], do, o, lse, lengths, ctx.scale, o.device)
+        return grads[0], grads[1], grads[2], None, None, None
+
+
+class _QAttnPackedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, lengths, heads, scale):
+        B, T, W = qkv.shape
+        Q = W // 12
+        qkv, row = _attn_rows(qkv, W)
+        es = qkv.element_size()
+        ptrs = [qkv.data_ptr() + i * Q * es for i in range(3)]
+        o, lse = _qattn_fwd(qkv.dtype, B, T, heads, Q // heads, [(row, 3 * Q)] * 3, ptrs, lengths, scale, qkv.device, qkv)
+        ctx.heads, ctx.scale = heads, scale
+        ctx.save_for_backward(qkv, o, lse, lengths)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse, lengths = ctx.saved_tensors
+        B, T, W = qkv.shape
+        Q = W // 12
+        qkv, do = qkv.contiguous(), do.contiguous()
+        es = qkv.element_size()
+        grad = torch.empty((B, T, W), dtype=qkv.dtype, device=qkv.device)       # ONE gradient: dq | dk | dv windows of every component
+        _qattn_bwd(qkv.dtype, B, T, ctx.heads, Q // ctx.heads, [(W, 3 * Q)] * 3, [qkv.data_ptr() + i * Q * es for i in range(3)],
+                   [grad.data_ptr() + i * Q * es for i in range(3)], do, o, lse, lengths, ctx.scale, qkv.device)
+        return grad, None, None, None
+
+
+def _qattn_check(what, x, width_mult, heads, lengths, scale):
+    _require_device(x, what)
+    heads = int(heads)
+    if x.dim() != 3 or x.numel() == 0 or heads < 1 or x.shape[-1] % (width_mult * heads):
+        raise ValueError('%s: needs a non-empty (B, T, %d Q) tensor with heads = %d dividing Q, got %s'
+                         % (what, width_mult, heads, tuple(x.shape)))
+    if lengths is not None:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (x.shape[0],) or lengths.device != x.device:
+            raise ValueError('%s: lengths must be an int32 tensor of shape (%d,) on %s' % (what, x.shape[0], x.device))
+        lengths = lengths.contiguous()
+    if scale is None:
+        scale = 0.0                                  # the library's default: 1 / sqrt(4 dq)
+    elif not 0.0 < float(scale) < float('inf'):
+        raise ValueError('%s: scale must be a positive finite number or None, got %r' % (what, scale))
+    return heads, lengths, scale
+
+
+def qattention(q, k, v, heads, lengths=None, scale=None):
+    """Quaternion multi-head self-attention (include/qk_attn.h).  q, k, v: (B, T, 4 Q) component-major r|i|j|k with Q = heads * dq;
+    head h owns units h * dq .. of every component.  o = softmax_{t' < n}(scale * <q_t, k_t'>) v over the 4 dq reals of a head, with
+    n = lengths[b]; rows t >= n are inactive: o = 0 exactly, no gradient, and nothing in them is read.  scale None: 1 / sqrt(4 dq).
+    Views with a unit column stride (column windows of a wider (B, T, W) buffer) are read in place.  Returns o (B, T, 4 Q); the
+    backward returns dq, dk, dv."""
+    heads, lengths, scale = _qattn_check('qattention', q, 4, heads, lengths, scale)
+    for name, t in (('k', k), ('v', v)):
+        if t.shape != q.shape or t.dtype != q.dtype or t.device != q.device:
+            raise ValueError('qattention: %s must match q (%s %s on %s)' % (name, q.dtype, tuple(q.shape), q.device))
+    return _QAttnFn.apply(q, k, v, lengths, heads, scale)
+
+
+def qattention_packed(qkv, heads, lengths=None, scale=None):
+    """qattention on the (B, T, 12 Q) output of ONE QuaternionDense with 3 Q quaternion units: component c holds q | k | v units at
+    columns c * 3Q + [0, Q), [Q, 2Q), [2Q, 3Q), read in place through the component strides.  The backward writes ONE (B, T, 12 Q)
+    gradient, so the projection's backward sees one dy and no cat."""
+    heads, lengths, scale = _qattn_check('qattention_packed', qkv, 12, heads, lengths, scale)
+    return _QAttnPackedFn.apply(qkv, lengths, heads, scale)

@@ -3,3 +3,4 @@ models/interspeech_model.py): callers of the quaternion hot path, kept as thin t
 from .example_model import CNN, DNN
 from .interspeech_model import getTimitModel2D, TimitQCNN
 from .qlstm_model import TimitQLSTM
+from .qtransformer_model import TimitQTransformer
