@@ -68,6 +68,13 @@ the same output layer, loss, decoding and evaluation; the frame counts of a batc
 are never attended to.  --tf-units = 64 or 128 times --tf-heads runs the attention on the matrix cores in bf16 / fp16.
 No phone error rate has been measured with it.
 
+--model qconformer trains qcnn_amd.models.TimitQConformer: the same projection and position table, --tf-layers macaron Conformer
+blocks (half-step feed-forward, QuaternionMultiHeadAttention, the convolution module -- a gated pointwise projection, a depthwise
+quaternion convolution of --conv-kernel taps over time in one fused kernel, layer normalisation, swish, a pointwise projection --
+half-step feed-forward, a closing normalisation) and the same output layer; the frame counts of a batch are the lengths of the
+attention and of the convolution, so padding frames are neither attended to nor convolved over.  The --tf-* options apply to it.
+Nobody has measured a phone error rate with it.
+
 --device-corpus packs TRAIN and TEST once into device memory (qcnn_amd.data.DeviceCorpus) and takes every training batch from
 DeviceCorpus.next_batch: one launch gathers the padded waveforms, lengths and labels of the next row of an EpochSampler, whose
 order is a keyed permutation of the length-sorted batches evaluated on the device -- real epochs (every batch once per epoch, a new
@@ -255,8 +262,9 @@ def main():
     ap.add_argument('--resume', default=None, metavar='PATH', help='continue from a checkpoint written by --checkpoint')
     ap.add_argument('--device-corpus', action='store_true',
                     help='keep TRAIN and TEST in device memory, shuffle epochs and assemble every batch on the device')
-    ap.add_argument('--model', default='qcnn', choices=['qcnn', 'qlstm', 'qtransformer'],
-                    help='qcnn: the reference model; qlstm: a stack of quaternion LSTM layers; qtransformer: quaternion self-attention encoder blocks')
+    ap.add_argument('--model', default='qcnn', choices=['qcnn', 'qlstm', 'qtransformer', 'qconformer'],
+                    help='qcnn: the reference model; qlstm: a stack of quaternion LSTM layers; qtransformer: quaternion self-attention encoder blocks; '
+                         'qconformer: Conformer blocks (self-attention + gated depthwise quaternion convolution)')
     ap.add_argument('--rnn-layers', type=int, default=4, help='qlstm: number of bidirectional QuaternionLSTM layers')
     ap.add_argument('--rnn-units', type=int, default=1024, help='qlstm: units per direction (a multiple of 64 runs on the matrix cores)')
     ap.add_argument('--layer-norm', action='store_true', help='qlstm: a quaternion layer normalisation behind every recurrent layer')
@@ -264,6 +272,7 @@ def main():
     ap.add_argument('--tf-units', type=int, default=512, help='qtransformer: model width (64 or 128 per head runs the attention on the matrix cores)')
     ap.add_argument('--tf-heads', type=int, default=8, help='qtransformer: attention heads (must divide tf-units / 4)')
     ap.add_argument('--tf-ff', type=int, default=2048, help='qtransformer: width of the feed-forward layer')
+    ap.add_argument('--conv-kernel', type=int, default=15, help='qconformer: taps of the depthwise convolution over time (1 .. 31)')
     args = ap.parse_args()
     if args.layer_norm and args.model != 'qlstm':
         ap.error('--layer-norm needs --model qlstm')
@@ -320,6 +329,12 @@ def main():
                                   l2=args.l2)
         print('model: %d quaternion transformer encoder blocks of %d units, %d heads, feed-forward %d'
               % (args.tf_layers, args.tf_units, args.tf_heads, args.tf_ff))
+    elif args.model == 'qconformer':
+        from qcnn_amd.models import TimitQConformer
+        model = TimitQConformer(num_layers=args.tf_layers, units=args.tf_units, heads=args.tf_heads, ff_units=args.tf_ff,
+                                kernel_size=args.conv_kernel, dropout=args.dropout, l2=args.l2)
+        print('model: %d quaternion Conformer blocks of %d units, %d heads, feed-forward %d, %d-tap depthwise convolution'
+              % (args.tf_layers, args.tf_units, args.tf_heads, args.tf_ff, args.conv_kernel))
     else:
         model, _ = getTimitModel2D(d)
     x0 = (to_device(train, batches[0][:1], dev, dtype) if corpus is None else device_batch(corpus.batch(batches[0][:1]), dtype))[0]

@@ -24,6 +24,7 @@ def _newest_header():
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_rnn.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_norm.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_attn.h'))
+    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_dwconv.h'))
     return max(os.path.getmtime(p) for p in deps)
 
 

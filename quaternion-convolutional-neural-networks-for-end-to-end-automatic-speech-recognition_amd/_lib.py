@@ -302,6 +302,27 @@ ATTN_SYMBOLS = {
     'qk_qattn_bwd': (ctypes.c_int, [_AD, _VP, _VP, _VP, _VP, _VP, _FP, _VP, ctypes.c_float, _VP, _VP, _VP, _VP, _SZ, _VP]),
 }
 
+# ---- include/qk_dwconv.h: depthwise quaternion convolution with a fused GLU gate (a seventh table, for the same reason) ----
+QK_QDWCONV_PATH_GENERIC, QK_QDWCONV_PATH_VEC = 1, 2
+QK_QDWCONV_PATH_NAMES = {0: 'none', QK_QDWCONV_PATH_GENERIC: 'generic', QK_QDWCONV_PATH_VEC: 'vec'}
+
+
+class QDWConvDesc(ctypes.Structure):
+    """qk_qdwconv_desc_t (include/qk_dwconv.h)"""
+    _fields_ = [('dtype', I32), ('batch', I32), ('steps', I32), ('units', I32), ('taps', I32), ('pad_lo', I32), ('x_row', I32),
+                ('x_comp', I32), ('y_row', I32), ('y_comp', I32), ('flags', I32)]
+
+
+_WD = ctypes.POINTER(QDWConvDesc)
+
+DWCONV_SYMBOLS = {
+    'qk_qdwconv_supported': (ctypes.c_int, [_WD]),
+    'qk_qdwconv_workspace_bytes': (_SZ, [_WD, I32]),
+    'qk_qdwconv_last_path': (ctypes.c_int, []),
+    'qk_qdwconv_fwd': (ctypes.c_int, [_WD, _VP, _VP, _FP, _FP, _VP, _VP, _VP]),
+    'qk_qdwconv_bwd': (ctypes.c_int, [_WD, _VP, _VP, _VP, _FP, _VP, _VP, _VP, _FP, _FP, _VP, _SZ, _VP]),
+}
+
 _lib = None
 
 
@@ -314,7 +335,7 @@ def lib():
                 'libqk_hip.so is not built (%s). Run `python -c "import __graft_entry__ as g; '
                 'g.build()"` -- the quaternion layers have no CPU or eager fallback.' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS, RNN_SYMBOLS, NORM_SYMBOLS, ATTN_SYMBOLS):
+        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS, RNN_SYMBOLS, NORM_SYMBOLS, ATTN_SYMBOLS, DWCONV_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(handle, name)
                 fn.restype, fn.argtypes = res, args

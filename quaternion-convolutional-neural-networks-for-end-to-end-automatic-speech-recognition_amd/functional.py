@@ -2544,3 +2544,122 @@ def qattention_packed(qkv, heads, lengths=None, scale=None):
     gradient, so the projection's backward sees one dy and no cat."""
     heads, lengths, scale = _qattn_check('qattention_packed', qkv, 12, heads, lengths, scale)
     return _QAttnPackedFn.apply(qkv, lengths, heads, scale)
+
+
+# ---- include/qk_dwconv.h: depthwise quaternion convolution over time with a fused GLU gate ----------------------------------------
+def qdwconv_desc(dtype, batch, steps, units, taps, pad_lo, x=None, y=None):
+    """qk_qdwconv_desc_t for (batch, steps, 4 * units) tensors; x, y are (row, comp) stride pairs in elements (default: dense rows of
+    4 Q columns, components Q apart)."""
+    Q = int(units)
+    xs, ys = [(4 * Q, Q) if s is None else (int(s[0]), int(s[1])) for s in (x, y)]
+    return L.QDWConvDesc(_DTYPES[dtype], int(batch), int(steps), Q, int(taps), int(pad_lo), xs[0], xs[1], ys[0], ys[1], 0)
+
+
+def qdwconv_pad_lo(taps, padding):
+    """Zeros in front of the sequence: 'same' (K - 1) // 2, 'causal' K - 1 (the convention of QuaternionConv1D)."""
+    if padding == 'same':
+        return (int(taps) - 1) // 2
+    if padding == 'causal':
+        return int(taps) - 1
+    raise ValueError("padding must be 'same' or 'causal', got %r" % (padding,))
+
+
+def qdwconv_path(dtype, batch, steps, units, taps=15, packed=False):
+    """'vec' / 'generic': the kernel family qk_qdwconv_fwd / qk_qdwconv_bwd run for dense (packed: (B, T, 8 Q) gated input), 16-byte
+    aligned tensors of this shape (qk_qdwconv_supported)."""
+    Q = int(units)
+    desc = qdwconv_desc(dtype, batch, steps, Q, taps, 0, (8 * Q, 2 * Q) if packed else None)
+    path = L.lib().qk_qdwconv_supported(ctypes.byref(desc))
+    if path == 0:
+        L.check(L.QK_ERR_INVALID_ARG, 'qk_qdwconv_supported')
+    return L.QK_QDWCONV_PATH_NAMES[path]
+
+
+def qdwconv_last_path():
+    """'vec' / 'generic': what this thread's most recent depthwise call launched (qk_qdwconv_last_path)."""
+    return L.QK_QDWCONV_PATH_NAMES[L.lib().qk_qdwconv_last_path()]
+
+
+class _QDWConvFn(torch.autograd.Function):
+    """x is (B, T, 4 Q), or with `gated` the packed (B, T, 8 Q): a | g inside every component."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, lengths, pad_lo, gated):
+        B, T, W = x.shape
+        Q = W // (8 if gated else 4)
+        x, row = _attn_rows(x, W)
+        comp = W // 4
+        es = x.element_size()
+        desc = qdwconv_desc(x.dtype, B, T, Q, kernel.shape[0], pad_lo, (row, comp))
+        y = torch.empty((B, T, 4 * Q), dtype=x.dtype, device=x.device)
+        with _on_device(x.device):
+            rc = L.lib().qk_qdwconv_fwd(ctypes.byref(desc), x.data_ptr(), x.data_ptr() + Q * es if gated else None, _ptr(kernel),
+                                        _ptr(bias), _ptr(lengths), _ptr(y), _stream(x))
+        L.check(rc, 'qk_qdwconv_fwd')
+        ctx.pad_lo, ctx.gated = pad_lo, gated
+        ctx.save_for_backward(x, kernel, lengths)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, kernel, lengths = ctx.saved_tensors
+        B, T, W = x.shape
+        gated = ctx.gated
+        Q = W // (8 if gated else 4)
+        dev = x.device
+        x = x.contiguous()                                  # the gradient is dense: so is its input
+        dy, yrow = _attn_rows(dy, 4 * Q)
+        es = x.element_size()
+        desc = qdwconv_desc(x.dtype, B, T, Q, kernel.shape[0], ctx.pad_lo, (W, W // 4), (yrow, Q))
+        grad = torch.empty((B, T, W), dtype=x.dtype, device=dev)      # gated: ONE gradient, da | dg windows of every component
+        dw = torch.empty(tuple(kernel.shape), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        dbias = torch.empty((4 * Q,), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        with _on_device(dev):
+            lib = L.lib()
+            n, ws = 0, None
+            if dw is not None or dbias is not None:
+                n = int(lib.qk_qdwconv_workspace_bytes(ctypes.byref(desc), L.QK_OP_BWD))
+                if n == 0:
+                    L.check(L.QK_ERR_INVALID_ARG, 'qk_qdwconv_workspace_bytes')
+                ws = torch.empty(n, dtype=torch.uint8, device=dev)
+            rc = lib.qk_qdwconv_bwd(ctypes.byref(desc), dy.data_ptr(), x.data_ptr(), x.data_ptr() + Q * es if gated else None,
+                                    _ptr(kernel), _ptr(lengths), grad.data_ptr(), grad.data_ptr() + Q * es if gated else None,
+                                    _ptr(dw), _ptr(dbias), _ptr(ws), n, _stream(x))
+        L.check(rc, 'qk_qdwconv_bwd')
+        return grad, dw, dbias, None, None, None
+
+
+def _qdwconv(what, x, mult, kernel, bias, lengths, padding):
+    _require_device(x, what)
+    if x.dim() != 3 or x.numel() == 0 or x.shape[-1] % mult:
+        raise ValueError('%s: needs a non-empty (B, T, %d Q) tensor, got %s' % (what, mult, tuple(x.shape)))
+    Q = x.shape[-1] // mult
+    if kernel.dim() != 2 or kernel.dtype != torch.float32 or kernel.shape[1] != 4 * Q or not 1 <= kernel.shape[0] <= 31 \
+            or kernel.device != x.device:
+        raise ValueError('%s: kernel must be float32 of shape (K, %d) with K in 1 .. 31 on %s, got %s %s'
+                         % (what, 4 * Q, x.device, kernel.dtype, tuple(kernel.shape)))
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (4 * Q,) or bias.device != x.device):
+        raise ValueError('%s: bias must be float32 of shape (%d,) on %s' % (what, 4 * Q, x.device))
+    if lengths is not None:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (x.shape[0],) or lengths.device != x.device:
+            raise ValueError('%s: lengths must be an int32 tensor of shape (%d,) on %s' % (what, x.shape[0], x.device))
+        lengths = lengths.contiguous()
+    return _QDWConvFn.apply(x, kernel.contiguous(), bias.contiguous() if bias is not None else None, lengths,
+                            qdwconv_pad_lo(kernel.shape[0], padding), mult == 8)
+
+
+def qdwconv1d(x, kernel, bias=None, lengths=None, padding='same'):
+    """Depthwise quaternion convolution over time (include/qk_dwconv.h).  x: (B, T, 4 Q) component-major r|i|j|k; kernel (K, 4 Q)
+    float32, K quaternion taps per unit, component-major per tap; bias (4 Q,) float32 or None.  y[t] = bias + sum_k W[k] (x) x[t + k -
+    pad_lo] per unit, the Hamilton product in the order of the convolution layers; nothing mixes units.  With n = lengths[b] the
+    sequence is zero outside [0, n) whatever x holds there, and rows t >= n give y = 0 exactly and take no gradient.  padding: 'same'
+    or 'causal'.  Views with a unit column stride are read in place.  The backward returns dx, dkernel, dbias."""
+    return _qdwconv('qdwconv1d', x, 4, kernel, bias, lengths, padding)
+
+
+def qglu_dwconv1d(u, kernel, bias=None, lengths=None, padding='same'):
+    """qdwconv1d of the gated input a * sigmoid(g), on the packed (B, T, 8 Q) output of ONE QuaternionDense with 2 Q quaternion
+    units: component c holds a | g at columns c * 2Q + [0, Q), [Q, 2Q), read in place through the component stride.  The gate is
+    evaluated once per element inside the kernel; the backward writes ONE (B, T, 8 Q) gradient, so the projection's backward sees
+    one dy and no cat.  Returns (B, T, 4 Q)."""
+    return _qdwconv('qglu_dwconv1d', u, 8, kernel, bias, lengths, padding)

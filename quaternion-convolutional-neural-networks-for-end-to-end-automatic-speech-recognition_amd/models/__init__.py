@@ -4,3 +4,4 @@ from .example_model import CNN, DNN
 from .interspeech_model import getTimitModel2D, TimitQCNN
 from .qlstm_model import TimitQLSTM
 from .qtransformer_model import TimitQTransformer
+from .qconformer_model import TimitQConformer
