@@ -75,6 +75,13 @@ half-step feed-forward, a closing normalisation) and the same output layer; the 
 attention and of the convolution, so padding frames are neither attended to nor convolved over.  The --tf-* options apply to it.
 Nobody has measured a phone error rate with it.
 
+--model qtransducer trains qcnn_amd.models.TimitQTransducer: --encoder qlstm | qtransformer | qconformer (built from the same
+--rnn-* / --tf-* / --conv-kernel options; its CTC output layer stays unused) under the transducer loss, with a quaternion LSTM
+prediction network of --pred-units over the label history and a joint network of --joint-units.  The loss is
+TimitQTransducer.training_loss (mean transducer cost + the l2 terms; three HIP launches for the cost and its gradient); with
+--eval-every the held-out batch is decoded greedily (time-synchronous, at most 4 symbols per frame) and scored with the same phone
+error rate.  --lm-order, --align-eval and --confusions belong to the CTC models.  Nobody has measured a phone error rate with it.
+
 --device-corpus packs TRAIN and TEST once into device memory (qcnn_amd.data.DeviceCorpus) and takes every training batch from
 DeviceCorpus.next_batch: one launch gathers the padded waveforms, lengths and labels of the next row of an EpochSampler, whose
 order is a keyed permutation of the length-sorted batches evaluated on the device -- real epochs (every batch once per epoch, a new
@@ -262,9 +269,13 @@ def main():
     ap.add_argument('--resume', default=None, metavar='PATH', help='continue from a checkpoint written by --checkpoint')
     ap.add_argument('--device-corpus', action='store_true',
                     help='keep TRAIN and TEST in device memory, shuffle epochs and assemble every batch on the device')
-    ap.add_argument('--model', default='qcnn', choices=['qcnn', 'qlstm', 'qtransformer', 'qconformer'],
+    ap.add_argument('--model', default='qcnn', choices=['qcnn', 'qlstm', 'qtransformer', 'qconformer', 'qtransducer'],
                     help='qcnn: the reference model; qlstm: a stack of quaternion LSTM layers; qtransformer: quaternion self-attention encoder blocks; '
-                         'qconformer: Conformer blocks (self-attention + gated depthwise quaternion convolution)')
+                         'qconformer: Conformer blocks (self-attention + gated depthwise quaternion convolution); '
+                         'qtransducer: one of the three sequence encoders (--encoder) under the transducer loss')
+    ap.add_argument('--encoder', default='qlstm', choices=['qlstm', 'qtransformer', 'qconformer'], help='qtransducer: the encoder')
+    ap.add_argument('--pred-units', type=int, default=256, help='qtransducer: width of the prediction network (a multiple of 4)')
+    ap.add_argument('--joint-units', type=int, default=512, help='qtransducer: width of the joint network (a multiple of 4)')
     ap.add_argument('--rnn-layers', type=int, default=4, help='qlstm: number of bidirectional QuaternionLSTM layers')
     ap.add_argument('--rnn-units', type=int, default=1024, help='qlstm: units per direction (a multiple of 64 runs on the matrix cores)')
     ap.add_argument('--layer-norm', action='store_true', help='qlstm: a quaternion layer normalisation behind every recurrent layer')
@@ -274,8 +285,12 @@ def main():
     ap.add_argument('--tf-ff', type=int, default=2048, help='qtransformer: width of the feed-forward layer')
     ap.add_argument('--conv-kernel', type=int, default=15, help='qconformer: taps of the depthwise convolution over time (1 .. 31)')
     args = ap.parse_args()
-    if args.layer_norm and args.model != 'qlstm':
-        ap.error('--layer-norm needs --model qlstm')
+    transducer = args.model == 'qtransducer'
+    body = args.encoder if transducer else args.model          # which encoder / CTC model is built
+    if args.layer_norm and body != 'qlstm':
+        ap.error('--layer-norm needs --model qlstm (or --model qtransducer --encoder qlstm)')
+    if transducer and (args.lm_order > 0 or args.align_eval or args.confusions > 0):
+        ap.error('--model qtransducer decodes greedily: --lm-order, --align-eval and --confusions belong to the CTC models')
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
     dtype = getattr(torch, args.dtype)
@@ -317,19 +332,19 @@ def main():
                               l2=args.l2, model='quaternion', quat_init='quaternion')
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
-    if args.model == 'qlstm':
+    if body == 'qlstm':
         from qcnn_amd.models import TimitQLSTM
         model = TimitQLSTM(num_layers=args.rnn_layers, units=args.rnn_units, bidirectional=True, dropout=args.dropout, l2=args.l2,
                            layer_norm=args.layer_norm)
         print('model: %d bidirectional quaternion LSTM layers of %d units%s' % (args.rnn_layers, args.rnn_units,
                                                                                 ', layer normalisation' if args.layer_norm else ''))
-    elif args.model == 'qtransformer':
+    elif body == 'qtransformer':
         from qcnn_amd.models import TimitQTransformer
         model = TimitQTransformer(num_layers=args.tf_layers, units=args.tf_units, heads=args.tf_heads, ff_units=args.tf_ff, dropout=args.dropout,
                                   l2=args.l2)
         print('model: %d quaternion transformer encoder blocks of %d units, %d heads, feed-forward %d'
               % (args.tf_layers, args.tf_units, args.tf_heads, args.tf_ff))
-    elif args.model == 'qconformer':
+    elif body == 'qconformer':
         from qcnn_amd.models import TimitQConformer
         model = TimitQConformer(num_layers=args.tf_layers, units=args.tf_units, heads=args.tf_heads, ff_units=args.tf_ff,
                                 kernel_size=args.conv_kernel, dropout=args.dropout, l2=args.l2)
@@ -337,7 +352,11 @@ def main():
               % (args.tf_layers, args.tf_units, args.tf_heads, args.tf_ff, args.conv_kernel))
     else:
         model, _ = getTimitModel2D(d)
-    x0 = (to_device(train, batches[0][:1], dev, dtype) if corpus is None else device_batch(corpus.batch(batches[0][:1]), dtype))[0]
+    if transducer:
+        from qcnn_amd.models import TimitQTransducer
+        model = TimitQTransducer(model, pred_units=args.pred_units, joint_units=args.joint_units, dropout=args.dropout, l2=args.l2)
+        print('transducer: the model above as encoder, prediction network of %d units, joint of %d units' % (args.pred_units, args.joint_units))
+    x0 =(to_device(train, batches[0][:1], dev, dtype) if corpus is None else device_batch(corpus.batch(batches[0][:1]), dtype))[0]
     with torch.no_grad():
         model(x0)                                                 # build-on-first-call, like Keras
     model.to(dev)
@@ -416,8 +435,8 @@ def main():
         with eval_weights():                                          # --ema: param and ema change places for the evaluation
             xe, ile, le, lle, starts = held_out_batch(held_out)
             res = model.evaluate(xe, le, ile, lle, class_map=class_map)
-            print('step %5d  held-out ctc cost %.4f  PER(39) %.4f (%d / %d)%s'
-                  % (step, float(res.loss), float(res.per), int(res.errors), int(res.symbols),
+            print('step %5d  held-out %s cost %.4f  PER(39) %.4f (%d / %d)%s'
+                  % (step, 'transducer' if transducer else 'ctc', float(res.loss), float(res.per), int(res.errors), int(res.symbols),
                      '  [averaged weights, ema %g]' % args.ema if opt is not None and args.ema > 0 else ''))
             if args.align_eval:
                 ali = model.align(xe, le, ile, lle)

@@ -25,6 +25,7 @@ def _newest_header():
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_norm.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_attn.h'))
     deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_dwconv.h'))
+    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_rnnt.h'))
     return max(os.path.getmtime(p) for p in deps)
 
 

@@ -323,6 +323,15 @@ DWCONV_SYMBOLS = {
     'qk_qdwconv_bwd': (ctypes.c_int, [_WD, _VP, _VP, _VP, _FP, _VP, _VP, _VP, _FP, _FP, _VP, _SZ, _VP]),
 }
 
+# ---- include/qk_rnnt.h: the transducer (RNN-T) loss (an eighth table, for the same reason) ----
+QK_RNNT_MAX_CLASSES, QK_RNNT_MAX_U1 = 256, 128
+
+RNNT_SYMBOLS = {
+    'qk_rnnt_supported': (ctypes.c_int, [I32, I32, I32, I32, I32]),
+    'qk_rnnt_workspace_bytes': (_SZ, [I32, I32, I32, I32]),
+    'qk_rnnt_loss': (ctypes.c_int, [I32, I32, I32, I32, I32, _VP, _VP, _VP, _VP, _FP, _VP, _VP, _SZ, _VP]),
+}
+
 _lib = None
 
 
@@ -335,7 +344,7 @@ def lib():
                 'libqk_hip.so is not built (%s). Run `python -c "import __graft_entry__ as g; '
                 'g.build()"` -- the quaternion layers have no CPU or eager fallback.' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS, RNN_SYMBOLS, NORM_SYMBOLS, ATTN_SYMBOLS, DWCONV_SYMBOLS):
+        for table in (SYMBOLS, OPT_SYMBOLS, DATA_SYMBOLS, RNN_SYMBOLS, NORM_SYMBOLS, ATTN_SYMBOLS, DWCONV_SYMBOLS, RNNT_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(handle, name)
                 fn.restype, fn.argtypes = res, args

@@ -1377,6 +1377,74 @@ def ctc_batch_cost(y_pred, labels, input_length, label_length, loss_scale=1.0):
     return _CtcFn.apply(y_pred.contiguous(), labels, input_length, label_length, loss_scale_arg(loss_scale, y_pred.device))
 
 
+# ---- transducer (RNN-T) loss (include/qk_rnnt.h) ------------------------------------------------------------------------------------
+def rnnt_supported(logits, labels):
+    """qk_rnnt_loss takes a contiguous (B, T, Lmax + 1, V) device tensor with labels (B, Lmax), within the limits of
+    include/qk_rnnt.h (2 <= V <= 256, Lmax <= 127, T >= 1)."""
+    if not (logits.is_cuda and logits.dtype in _DTYPES and logits.dim() == 4 and labels.dim() == 2 and logits.shape[0] > 0
+            and labels.shape[0] == logits.shape[0] and labels.shape[1] + 1 == logits.shape[2]):
+        return False
+    b, t, u1, v = logits.shape
+    return bool(L.lib().qk_rnnt_supported(_DTYPES[logits.dtype], b, t, u1, v))
+
+
+def _rnnt_call(logits, labels, input_length, label_length, want_grad):
+    if logits.dim() != 4:
+        raise ValueError('rnnt_loss: logits must be (B, T, Lmax + 1, V), got shape %s' % (tuple(logits.shape),))
+    b, t, u1, v = logits.shape
+    lab = labels.to(device=logits.device, dtype=torch.int32).reshape(b, -1).contiguous()
+    if lab.shape[1] + 1 != u1:
+        raise ValueError('rnnt_loss: logits have %d label positions, labels (B, %d) need %d' % (u1, lab.shape[1], lab.shape[1] + 1))
+    il = input_length.reshape(-1).to(device=logits.device, dtype=torch.int32).contiguous()
+    ll = label_length.reshape(-1).to(device=logits.device, dtype=torch.int32).contiguous()
+    if il.numel() != b or ll.numel() != b:
+        raise ValueError('rnnt_loss: input_length and label_length must have %d elements' % b)
+    cost = torch.empty(b, dtype=torch.float32, device=logits.device)
+    grad = torch.empty_like(logits) if want_grad else None
+    n = int(L.lib().qk_rnnt_workspace_bytes(b, t, u1, v))
+    ws = torch.empty(max(n, 16), dtype=torch.uint8, device=logits.device)
+    with _on_device(logits.device):
+        rc = L.lib().qk_rnnt_loss(_DTYPES[logits.dtype], b, t, u1, v, _ptr(logits), _ptr(lab) if lab.numel() else None, _ptr(il),
+                                  _ptr(ll), _ptr(cost), _ptr(grad), _ptr(ws), n, _stream(logits))
+    L.check(rc, 'qk_rnnt_loss')
+    return cost, grad
+
+
+class _RnntFn(torch.autograd.Function):
+    """qk_rnnt_loss: cost and d cost / d logits from one call; the backward only scales the stored gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, input_length, label_length, loss_scale=1.0):
+        cost, grad = _rnnt_call(logits, labels, input_length, label_length, ctx.needs_input_grad[0])
+        ctx.save_for_backward(grad)
+        ctx.loss_scale = loss_scale if isinstance(loss_scale, torch.Tensor) else float(loss_scale)
+        return cost.reshape(-1, 1)
+
+    @staticmethod
+    def backward(ctx, dcost):
+        grad, = ctx.saved_tensors
+        if isinstance(ctx.loss_scale, torch.Tensor) or ctx.loss_scale != 1.0:
+            # the product is formed in fp32 and rounded once, as in _CtcFn
+            return (grad.float() * (dcost.reshape(-1, 1, 1, 1).float() * ctx.loss_scale)).to(grad.dtype), None, None, None, None
+        return grad * dcost.reshape(-1, 1, 1, 1).to(grad.dtype), None, None, None, None
+
+
+def rnnt_cost_and_grad(logits, labels, input_length, label_length):
+    """(cost (B,), d cost / d logits) of qk_rnnt_loss as plain tensors (no autograd node)."""
+    _require_device(logits, 'rnnt_cost_and_grad')
+    return _rnnt_call(logits.contiguous(), labels, input_length, label_length, True)
+
+
+def rnnt_loss(logits, labels, input_length, label_length, loss_scale=1.0):
+    """Transducer (RNN-T) cost per sample, (B, 1) float32, of the joint's UNNORMALISED outputs logits (B, T, Lmax + 1, V), blank =
+    V - 1 (include/qk_rnnt.h has the recursion, the fused log-softmax gradient and the conventions for padding cells and
+    infeasible rows).  labels (B, Lmax) int; input_length, label_length (B,) or (B, 1).  Three launches; the gradient is stored by
+    the forward and the backward only scales it.  loss_scale multiplies the GRADIENT sent back (not the cost), exactly as in
+    ctc_batch_cost: a number or a one-element float32 device tensor."""
+    _require_device(logits, 'rnnt_loss')
+    return _RnntFn.apply(logits.contiguous(), labels, input_length, label_length, loss_scale_arg(loss_scale, logits.device))
+
+
 # ---- CTC decoding (include/qk.h, "CTC decoding") ----------------------------------------------------------------------------------
 CTC_MAX_BEAM, CTC_MAX_CLASSES, EDIT_MAX_REF = 128, 256, 1024
 

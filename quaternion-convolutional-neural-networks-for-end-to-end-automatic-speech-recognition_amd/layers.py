@@ -430,6 +430,63 @@ def ctc_batch_cost(y_pred, labels, input_length, label_length, blank=None, loss_
     return loss.reshape(-1, 1)
 
 
+def rnnt_batch_cost(logits, labels, input_length, label_length, loss_scale=1.0):
+    """Transducer (RNN-T) cost per sample, (B, 1), of the joint's unnormalised outputs logits (B, T, Lmax + 1, V), blank = V - 1:
+    the twin of ctc_batch_cost (include/qk_rnnt.h has the recursion and the conventions; functional.rnnt_loss is the device path,
+    three HIP launches, and a device tensor of a shape it does not take is an error, never a detour).  labels (B, Lmax) int;
+    input_length, label_length (B,) or (B, 1), clamped to [0, T] and [0, Lmax].  A row with input_length 0 or a label outside
+    [0, V - 2] costs +inf and sends no gradient; cells at or past a row's lengths are never used and receive none.
+    loss_scale multiplies the gradient sent back, not the cost.
+
+    CPU tensors take a plain torch path -- log_softmax, then alpha one anti-diagonal at a time, autograd for the gradient -- that
+    only needs to be correct: it is what the definition-level tests compare with."""
+    if logits.is_cuda:
+        return Fq.rnnt_loss(logits, labels, input_length, label_length, loss_scale=loss_scale)
+    return rnnt_cost_composed(logits, labels, input_length, label_length, loss_scale=loss_scale)
+
+
+def rnnt_cost_composed(logits, labels, input_length, label_length, loss_scale=1.0):
+    """rnnt_batch_cost composed from torch ops on whatever device the logits are on: the CPU path of rnnt_batch_cost, and the
+    composition tools/rnnt_time.py times the kernels against (one launch per operation and anti-diagonal, autograd through all)."""
+    if logits.dim() != 4 or labels.dim() != 2 or labels.shape[1] + 1 != logits.shape[2]:
+        raise ValueError('rnnt_batch_cost: logits (B, T, Lmax + 1, V) and labels (B, Lmax) expected, got %s and %s'
+                         % (tuple(logits.shape), tuple(labels.shape)))
+    b, t_max, u1, v = logits.shape
+    lmax = u1 - 1
+    x = logits.float()
+    dev = x.device
+    if isinstance(loss_scale, torch.Tensor) or loss_scale != 1.0:
+        x = _GradScale.apply(x, loss_scale)
+    tb = input_length.reshape(-1).to(dev).long().clamp(0, t_max)
+    ub = label_length.reshape(-1).to(dev).long().clamp(0, lmax)
+    lab = labels.to(dev).long()
+    t_idx, u_idx = torch.arange(t_max, device=dev), torch.arange(u1, device=dev)
+    active = (t_idx[None, :, None] < tb[:, None, None]) & (u_idx[None, None, :] <= ub[:, None, None])
+    in_label = torch.arange(lmax, device=dev)[None, :] < ub[:, None]
+    feasible = (tb > 0) & ~(in_label & ((lab < 0) | (lab > v - 2))).any(dim=1)
+    # padding cells are SELECTED away in front of the softmax: a NaN there reaches neither the cost nor the gradient
+    lp = torch.log_softmax(torch.where(active[..., None], x, torch.zeros((), dtype=x.dtype, device=dev)), dim=-1)
+    lpb = lp[..., v - 1]                                                                  # (B, T, U1)
+    lpl = torch.gather(lp[:, :, :lmax, :], 3, lab.clamp(0, v - 1)[:, None, :, None].expand(b, t_max, lmax, 1))[..., 0]
+    neg = torch.full((), float('-inf'), dtype=x.dtype, device=dev)
+    alpha = torch.full((b, t_max, u1), float('-inf'), dtype=x.dtype, device=dev)
+    alpha[:, 0, 0] = 0.0
+    for d in range(1, t_max + u1 - 1):
+        us = torch.arange(max(0, d - t_max + 1), min(d, u1 - 1) + 1, device=dev)
+        ts = d - us
+        tp, up = (ts - 1).clamp(min=0), (us - 1).clamp(min=0)
+        top = torch.where((ts > 0)[None, :], alpha[:, tp, us] + lpb[:, tp, us], neg)
+        if lmax:
+            left = torch.where((us > 0)[None, :], alpha[:, ts, up] + lpl[:, ts, up.clamp(max=lmax - 1)], neg)
+        else:
+            left = neg.expand_as(top)
+        alpha[:, ts, us] = torch.logaddexp(top, left)
+    rows = torch.arange(b, device=dev)
+    te = (tb - 1).clamp(min=0)
+    ll = alpha[rows, te, ub] + lpb[rows, te, ub]
+    return torch.where(feasible, -ll, torch.full((), float('inf'), dtype=x.dtype, device=dev)).reshape(-1, 1)
+
+
 def ctc_decode(y_pred, input_length, greedy=True, beam_width=100, top_paths=1, merge_repeated=True, lm=None, lm_weight=0.5,
                insertion_bonus=0.0, lm_eos=True):
     """K.ctc_decode(y_pred, input_length, greedy, beam_width, top_paths) on the device (functional.ctc_greedy_decode /

@@ -5,3 +5,4 @@ from .interspeech_model import getTimitModel2D, TimitQCNN
 from .qlstm_model import TimitQLSTM
 from .qtransformer_model import TimitQTransformer
 from .qconformer_model import TimitQConformer
+from .qtransducer_model import TimitQTransducer
