@@ -18,14 +18,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-
 
 def _newest_header():
     deps = glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(CSRC, '*.inc'))
-    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk.h'))
-    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_opt.h'))
-    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_data.h'))
-    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_rnn.h'))
-    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_norm.h'))
-    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_attn.h'))
-    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_dwconv.h'))
-    deps.append(os.path.join(os.path.dirname(HERE), 'include', 'qk_rnnt.h'))
+    deps += glob.glob(os.path.join(os.path.dirname(HERE), 'include', '*.h'))
     return max(os.path.getmtime(p) for p in deps)
 
 

@@ -17,6 +17,7 @@
 // dimension, the other side one row at a time, every dot product a wave butterfly; fp32 throughout (the 16-bit types round p and
 // dS at the header's rounding points).  Correct before fast.
 #include "qk_common.h"
+#include "qk_seq.h"
 #include "../../include/qk_attn.h"
 
 #include <math.h>
@@ -27,18 +28,7 @@ namespace {
 constexpr float kQaLog2e = 1.4426950408889634f;
 constexpr float kQaLn2 = 0.6931471805599453f;
 
-typedef _Float16 qa_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 qa_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short qa_u16;
-
-__device__ __forceinline__ floatx4 qa_mfma(bf16, const uint4 &a, const uint4 &b, const floatx4 &c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(qa_bf16x8, a), __builtin_bit_cast(qa_bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ floatx4 qa_mfma(f16, const uint4 &a, const uint4 &b, const floatx4 &c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(qa_f16x8, a), __builtin_bit_cast(qa_f16x8, b), c, 0, 0, 0);
-}
 
 __device__ __forceinline__ unsigned qa_bits(bf16 v) { return v.x; }
 __device__ __forceinline__ unsigned qa_bits(f16 v) { return __builtin_bit_cast(qa_u16, v); }
@@ -50,9 +40,6 @@ __device__ __forceinline__ uint4 qa_pack_acc(const floatx4 &a, const floatx4 &b)
 {
     return make_uint4(qa_pack2<T>(a[0], a[1]), qa_pack2<T>(a[2], a[3]), qa_pack2<T>(b[0], b[1]), qa_pack2<T>(b[2], b[3]));
 }
-// the value a 16-bit path keeps at a rounding point (fp32: unchanged)
-template <typename T> __device__ __forceinline__ float qa_round(float v) { return to_f32(from_f32<T>(v)); }
-template <> __device__ __forceinline__ float qa_round<float>(float v) { return v; }
 
 struct QaArgs {
     int B, T, H, dq;
@@ -169,7 +156,7 @@ __global__ __launch_bounds__(256) void k_qattn_fwd(const QaArgs a)
         for (int sub = 0; sub < 4; ++sub) {
             s[sub] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) s[sub] = qa_mfma(T(), qa_frag_rm<D>(k_rm, 16 * sub + c16, 32 * ks + 8 * g), qf[ks], s[sub]);
+            for (int ks = 0; ks < KS; ++ks) s[sub] = mfma16(T(), qa_frag_rm<D>(k_rm, 16 * sub + c16, 32 * ks + 8 * g), qf[ks], s[sub]);
         }
         float mx = -INFINITY;
 #pragma unroll
@@ -202,7 +189,7 @@ __global__ __launch_bounds__(256) void k_qattn_fwd(const QaArgs a)
         for (int kk = 0; kk < 2; ++kk) {
             const uint4 pf = qa_pack_acc<T>(s[2 * kk], s[2 * kk + 1]);
 #pragma unroll
-            for (int dt = 0; dt < DT; ++dt) o[dt] = qa_mfma(T(), qa_frag_tr<TS>(v_tr, 16 * dt + c16, 32 * kk, g), pf, o[dt]);
+            for (int dt = 0; dt < DT; ++dt) o[dt] = mfma16(T(), qa_frag_tr<TS>(v_tr, 16 * dt + c16, 32 * kk, g), pf, o[dt]);
         }
     }
     l += __shfl_xor(l, 16, 64);
@@ -257,8 +244,8 @@ __global__ __launch_bounds__(256) void k_qattn_bwd_q(const QaArgs a)
             floatx4 s = floatx4{0.f, 0.f, 0.f, 0.f}, dp = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                s = qa_mfma(T(), qa_frag_rm<D>(k_rm, 16 * sub + c16, 32 * ks + 8 * g), qf[ks], s);
-                dp = qa_mfma(T(), qa_frag_rm<D>(v_rm, 16 * sub + c16, 32 * ks + 8 * g), gf[ks], dp);
+                s = mfma16(T(), qa_frag_rm<D>(k_rm, 16 * sub + c16, 32 * ks + 8 * g), qf[ks], s);
+                dp = mfma16(T(), qa_frag_rm<D>(v_rm, 16 * sub + c16, 32 * ks + 8 * g), gf[ks], dp);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -269,7 +256,7 @@ __global__ __launch_bounds__(256) void k_qattn_bwd_q(const QaArgs a)
         }
         const uint4 df = qa_pack_acc<T>(ds[0], ds[1]);
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) acc[dt] = qa_mfma(T(), qa_frag_tr<TS>(k_tr, 16 * dt + c16, 0, g), df, acc[dt]);
+        for (int dt = 0; dt < DT; ++dt) acc[dt] = mfma16(T(), qa_frag_tr<TS>(k_tr, 16 * dt + c16, 0, g), df, acc[dt]);
     }
     if (tq < a.T)
         qa_store_rows<T, DQ>((qa_u16 *)a.d_q + (size_t)b * a.T * a.q_row + head, a.q_row, a.q_comp, tq, active, g, acc, 1.f);
@@ -323,8 +310,8 @@ __global__ __launch_bounds__(256) void k_qattn_bwd_kv(const QaArgs a)
             floatx4 s = floatx4{0.f, 0.f, 0.f, 0.f}, dp = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                s = qa_mfma(T(), qa_frag_rm<D>(q_rm, 16 * sub + c16, 32 * ks + 8 * g), kf[ks], s);
-                dp = qa_mfma(T(), qa_frag_rm<D>(g_rm, 16 * sub + c16, 32 * ks + 8 * g), vf[ks], dp);
+                s = mfma16(T(), qa_frag_rm<D>(q_rm, 16 * sub + c16, 32 * ks + 8 * g), kf[ks], s);
+                dp = mfma16(T(), qa_frag_rm<D>(g_rm, 16 * sub + c16, 32 * ks + 8 * g), vf[ks], dp);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -337,8 +324,8 @@ __global__ __launch_bounds__(256) void k_qattn_bwd_kv(const QaArgs a)
         const uint4 pf = qa_pack_acc<T>(p[0], p[1]), df = qa_pack_acc<T>(ds[0], ds[1]);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-            dv[dt] = qa_mfma(T(), qa_frag_tr<TS>(g_tr, 16 * dt + c16, 0, g), pf, dv[dt]);
-            dk[dt] = qa_mfma(T(), qa_frag_tr<TS>(q_tr, 16 * dt + c16, 0, g), df, dk[dt]);
+            dv[dt] = mfma16(T(), qa_frag_tr<TS>(g_tr, 16 * dt + c16, 0, g), pf, dv[dt]);
+            dk[dt] = mfma16(T(), qa_frag_tr<TS>(q_tr, 16 * dt + c16, 0, g), df, dk[dt]);
         }
     }
     if (tk < a.T) {
@@ -444,7 +431,7 @@ __global__ __launch_bounds__(256) void k_qattn_fwd_gen(const QaArgs a)
             const int d = d0 + lane;
             float acc = 0.f;
             for (int j = 0; j < n; ++j) {
-                const float p = qa_round<T>(expf(a.scale * qa_dot(qrow, a.q_comp, kb + (size_t)j * a.k_row, a.k_comp, a.dq, lane) - ls));
+                const float p = round_to<T>(expf(a.scale * qa_dot(qrow, a.q_comp, kb + (size_t)j * a.k_row, a.k_comp, a.dq, lane) - ls));
                 if (d < D) acc += p * to_f32(vb[(size_t)j * a.v_row + qa_col(d, a.dq, a.v_comp)]);
             }
             if (d < D) orow[qa_col(d, a.dq, a.o_comp)] = from_f32<T>(acc);
@@ -481,7 +468,7 @@ __global__ __launch_bounds__(256) void k_qattn_bwd_q_gen(const QaArgs a)
                 const T *krow = kb + (size_t)j * a.k_row;
                 const float p = expf(a.scale * qa_dot(qrow, a.q_comp, krow, a.k_comp, a.dq, lane) - ls);
                 const float dp = qa_dot(grow, a.o_comp, vb + (size_t)j * a.v_row, a.v_comp, a.dq, lane);
-                const float ds = qa_round<T>(p * (dp - dl) * a.scale);
+                const float ds = round_to<T>(p * (dp - dl) * a.scale);
                 if (d < D) acc += ds * to_f32(krow[qa_col(d, a.dq, a.k_comp)]);
             }
             if (d < D) dqrow[qa_col(d, a.dq, a.q_comp)] = from_f32<T>(acc);
@@ -521,9 +508,9 @@ __global__ __launch_bounds__(256) void k_qattn_bwd_kv_gen(const QaArgs a)
                 const T *qrow = qb + (size_t)i * a.q_row, *grow = gb + (size_t)i * a.o_row;
                 const float p = expf(a.scale * qa_dot(qrow, a.q_comp, krow, a.k_comp, a.dq, lane) - a.lse[stat + i]);
                 const float dp = qa_dot(grow, a.o_comp, vrow, a.v_comp, a.dq, lane);
-                const float ds = qa_round<T>(p * (dp - a.delta[stat + i]) * a.scale);
+                const float ds = round_to<T>(p * (dp - a.delta[stat + i]) * a.scale);
                 if (d < D) {
-                    av += qa_round<T>(p) * to_f32(grow[qa_col(d, a.dq, a.o_comp)]);
+                    av += round_to<T>(p) * to_f32(grow[qa_col(d, a.dq, a.o_comp)]);
                     ak += ds * to_f32(qrow[qa_col(d, a.dq, a.q_comp)]);
                 }
             }
@@ -547,8 +534,7 @@ bool qa_stride_ok(const char *what, const char *name, int row, int comp, int uni
 
 bool qa_desc_ok(const qk_qattn_desc_t *d, const char *what)
 {
-    if (!d) { set_error("%s: NULL descriptor", what); return false; }
-    if (d->dtype != QK_F32 && d->dtype != QK_BF16 && d->dtype != QK_F16) { set_error("%s: unknown dtype %d", what, d->dtype); return false; }
+    if (!desc_head_ok(d, what)) return false;
     if (d->batch < 1 || d->steps < 1 || d->heads < 1 || d->dq < 1) {
         set_error("%s: batch, steps, heads and dq must be >= 1 (got %d, %d, %d, %d)", what, d->batch, d->steps, d->heads, d->dq);
         return false;
@@ -574,16 +560,6 @@ int qa_path(const qk_qattn_desc_t *d)
     return QK_QATTN_PATH_MFMA;
 }
 
-bool qa_aligned(const void *p, size_t al) { return ((uintptr_t)p & (al - 1)) == 0; }
-
-int qa_launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return QK_OK;
-    set_error("%s: kernel launch failed: %s", what, hipGetErrorString(e));
-    return QK_ERR_LAUNCH;
-}
-
 QaArgs qa_args(const qk_qattn_desc_t *d, float scale, const int32_t *lengths)
 {
     QaArgs a = {};
@@ -595,7 +571,7 @@ QaArgs qa_args(const qk_qattn_desc_t *d, float scale, const int32_t *lengths)
     return a;
 }
 
-size_t qa_delta_bytes(const qk_qattn_desc_t *d) { return ((size_t)d->batch * d->heads * d->steps * sizeof(float) + 255) / 256 * 256; }
+size_t qa_delta_bytes(const qk_qattn_desc_t *d) { return align256((size_t)d->batch * d->heads * d->steps * sizeof(float)); }
 int qa_wave_grid(const qk_qattn_desc_t *d)
 {
     const long long blocks = ((long long)d->batch * d->heads * d->steps + 3) / 4;
@@ -663,8 +639,7 @@ size_t qk_qattn_workspace_bytes(const qk_qattn_desc_t *desc, int32_t op)
     if (!qa_desc_ok(desc, "qk_qattn_workspace_bytes")) return 0;
     if (op == QK_OP_FWD) return 0;
     if (op == QK_OP_BWD) return qa_delta_bytes(desc);
-    set_error("qk_qattn_workspace_bytes: op must be QK_OP_FWD or QK_OP_BWD (got %d)", op);
-    return 0;
+    return bad_op("qk_qattn_workspace_bytes", op);
 }
 
 int qk_qattn_fwd(const qk_qattn_desc_t *desc, const void *q, const void *k, const void *v, const int32_t *lengths, float scale,
@@ -674,19 +649,18 @@ int qk_qattn_fwd(const qk_qattn_desc_t *desc, const void *q, const void *k, cons
     if (!qa_desc_ok(desc, what)) return QK_ERR_INVALID_ARG;
     if (!q || !k || !v || !o || !lse) { set_error("%s: NULL buffer", what); return QK_ERR_INVALID_ARG; }
     if (!isfinite(scale)) { set_error("%s: scale must be finite", what); return QK_ERR_INVALID_ARG; }
-    const size_t es = desc->dtype == QK_F32 ? 4 : 2;
-    if (!qa_aligned(q, es) || !qa_aligned(k, es) || !qa_aligned(v, es) || !qa_aligned(o, es) || !qa_aligned(lse, 4) || !qa_aligned(lengths, 4)) {
+    const size_t es = elem_size(desc->dtype);
+    if (!aligned(q, es) || !aligned(k, es) || !aligned(v, es) || !aligned(o, es) || !aligned(lse, 4) || !aligned(lengths, 4)) {
         set_error("%s: misaligned buffer", what);
         return QK_ERR_INVALID_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
     QaArgs a = qa_args(desc, scale, lengths);
     a.q = q; a.k = k; a.v = v; a.out_o = o; a.lse_out = lse;
-    const bool mfma = qa_path(desc) == QK_QATTN_PATH_MFMA && qa_aligned(q, 16) && qa_aligned(k, 16) && qa_aligned(v, 16) && qa_aligned(o, 16);
-    if (desc->dtype == QK_F32) qa_launch_fwd_gen<float>(desc, a, st);
-    else if (desc->dtype == QK_BF16) { if (mfma) qa_launch_fwd_mfma<bf16>(desc, a, st); else qa_launch_fwd_gen<bf16>(desc, a, st); }
-    else { if (mfma) qa_launch_fwd_mfma<f16>(desc, a, st); else qa_launch_fwd_gen<f16>(desc, a, st); }
-    return qa_launched(what);
+    const bool mfma = qa_path(desc) == QK_QATTN_PATH_MFMA && aligned(q, 16) && aligned(k, 16) && aligned(v, 16) && aligned(o, 16);
+    if (mfma) by_dtype16(desc->dtype, [&](auto t) { qa_launch_fwd_mfma<decltype(t)>(desc, a, st); });      // (qa_path: never fp32)
+    else by_dtype(desc->dtype, [&](auto t) { qa_launch_fwd_gen<decltype(t)>(desc, a, st); });
+    return launched(what);
 }
 
 int qk_qattn_bwd(const qk_qattn_desc_t *desc, const void *d_o, const void *q, const void *k, const void *v, const void *o,
@@ -697,23 +671,22 @@ int qk_qattn_bwd(const qk_qattn_desc_t *desc, const void *d_o, const void *q, co
     if (!qa_desc_ok(desc, what)) return QK_ERR_INVALID_ARG;
     if (!d_o || !q || !k || !v || !o || !lse || !d_q || !d_k || !d_v) { set_error("%s: NULL buffer", what); return QK_ERR_INVALID_ARG; }
     if (!isfinite(scale)) { set_error("%s: scale must be finite", what); return QK_ERR_INVALID_ARG; }
-    const size_t es = desc->dtype == QK_F32 ? 4 : 2;
-    if (!qa_aligned(q, es) || !qa_aligned(k, es) || !qa_aligned(v, es) || !qa_aligned(o, es) || !qa_aligned(d_o, es) || !qa_aligned(d_q, es)
-        || !qa_aligned(d_k, es) || !qa_aligned(d_v, es) || !qa_aligned(lse, 4) || !qa_aligned(lengths, 4) || !qa_aligned(workspace, 16)) {
+    const size_t es = elem_size(desc->dtype);
+    if (!aligned(q, es) || !aligned(k, es) || !aligned(v, es) || !aligned(o, es) || !aligned(d_o, es) || !aligned(d_q, es)
+        || !aligned(d_k, es) || !aligned(d_v, es) || !aligned(lse, 4) || !aligned(lengths, 4) || !aligned(workspace, 16)) {
         set_error("%s: misaligned buffer (16 bytes for the workspace)", what);
         return QK_ERR_INVALID_ARG;
     }
     const size_t need = qa_delta_bytes(desc);
-    if (!workspace || workspace_bytes < need) { set_error("%s: workspace of %zu bytes needed, %zu given", what, need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    if (workspace_ok(what, workspace, workspace_bytes, need) != QK_OK) return QK_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     QaArgs a = qa_args(desc, scale, lengths);
     a.q = q; a.k = k; a.v = v; a.o = o; a.d_o = d_o; a.lse = lse; a.d_q = d_q; a.d_k = d_k; a.d_v = d_v; a.delta = (float *)workspace;
-    const bool mfma = qa_path(desc) == QK_QATTN_PATH_MFMA && qa_aligned(q, 16) && qa_aligned(k, 16) && qa_aligned(v, 16) && qa_aligned(o, 16)
-                      && qa_aligned(d_o, 16) && qa_aligned(d_q, 16) && qa_aligned(d_k, 16) && qa_aligned(d_v, 16);
-    if (desc->dtype == QK_F32) qa_launch_bwd<float>(desc, false, a, st);
-    else if (desc->dtype == QK_BF16) { qa_launch_bwd<bf16>(desc, mfma, a, st); if (mfma) qa_launch_bwd_mfma<bf16>(desc, a, st); }
-    else { qa_launch_bwd<f16>(desc, mfma, a, st); if (mfma) qa_launch_bwd_mfma<f16>(desc, a, st); }
-    return qa_launched(what);
+    const bool mfma = qa_path(desc) == QK_QATTN_PATH_MFMA && aligned(q, 16) && aligned(k, 16) && aligned(v, 16) && aligned(o, 16)
+                      && aligned(d_o, 16) && aligned(d_q, 16) && aligned(d_k, 16) && aligned(d_v, 16);
+    by_dtype(desc->dtype, [&](auto t) { qa_launch_bwd<decltype(t)>(desc, mfma, a, st); });
+    if (mfma) by_dtype16(desc->dtype, [&](auto t) { qa_launch_bwd_mfma<decltype(t)>(desc, a, st); });      // (qa_path: never fp32)
+    return launched(what);
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 // Generic kernels (QK_QDWCONV_PATH_GENERIC): any width, stride and alignment; a thread per (row, unit) with plain loops over the
 // taps (the gate is re-evaluated per tap: correct before fast), a thread per (slab, tap, unit) for the weight partials.
 #include "qk_common.h"
+#include "qk_seq.h"
 #include "../../include/qk_dwconv.h"
 
 #include <math.h>
@@ -37,56 +38,6 @@ constexpr int kDwMaxSlabs = 128;
 constexpr int kDwMaxTaps = 31;
 
 thread_local int g_dw_path = 0;
-
-typedef _Float16 dw_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 dw_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float dw_f32x8 __attribute__((ext_vector_type(8)));
-
-// V activation elements in one 16-byte register group
-template <typename T> struct DwVec;
-template <> struct DwVec<float> {
-    static constexpr int V = 4;
-    static __device__ __forceinline__ void unpack(const uint4 &r, float (&o)[4])
-    {
-        o[0] = __uint_as_float(r.x); o[1] = __uint_as_float(r.y); o[2] = __uint_as_float(r.z); o[3] = __uint_as_float(r.w);
-    }
-    static __device__ __forceinline__ uint4 pack(const float (&v)[4])
-    {
-        return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
-    }
-};
-template <> struct DwVec<bf16> {
-    static constexpr int V = 8;
-    static __device__ __forceinline__ void unpack(const uint4 &r, float (&o)[8])
-    {
-        const unsigned w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { o[2 * i] = __uint_as_float(w[i] << 16); o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-    }
-    static __device__ __forceinline__ uint4 pack(const float (&v)[8])
-    {
-        dw_f32x8 f;                      // round-to-nearest-even by the packed conversion of gfx950
-#pragma unroll
-        for (int i = 0; i < 8; ++i) f[i] = v[i];
-        return __builtin_bit_cast(uint4, __builtin_convertvector(f, dw_bf16x8));
-    }
-};
-template <> struct DwVec<f16> {
-    static constexpr int V = 8;
-    static __device__ __forceinline__ void unpack(const uint4 &r, float (&o)[8])
-    {
-        const dw_f16x8 h = __builtin_bit_cast(dw_f16x8, r);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (float)h[i];
-    }
-    static __device__ __forceinline__ uint4 pack(const float (&v)[8])
-    {
-        dw_f16x8 h;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) h[i] = (f16)v[i];
-        return __builtin_bit_cast(uint4, h);
-    }
-};
 
 struct DwArgs {
     int B, T, Q, K, pad;             // pad: pad_lo of the descriptor
@@ -124,18 +75,13 @@ __device__ __forceinline__ void dw_ham_conj(float (&acc)[4], const float (&d)[4]
     acc[3] = fmaf(d[2], h[1], fmaf(-d[1], h[2], fmaf(-d[0], h[3], fmaf(d[3], h[0], acc[3]))));
 }
 
-template <typename T>
-__device__ __forceinline__ uint4 dw_load16(const T *p) { return *reinterpret_cast<const uint4 *>(p); }
-template <typename T>
-__device__ __forceinline__ void dw_store16(T *p, const uint4 &v) { *reinterpret_cast<uint4 *>(p) = v; }
-
 // Stage `frames` frames, the first one frame t_first of batch row b, of the 32 units from ub on into sh ([frame][4][32] fp32).
 // GATED: src = a, gate = g (may be NULL): h = a * sigmoid(g); else src as it is.  Frames outside [0, n) and units >= Q: zeros.
 template <typename T>
 __device__ __forceinline__ void dw_stage(float *sh, int frames, int t_first, int n, size_t row0, int row, int comp, int ub, int Q,
                                          const T *src, const T *gate)
 {
-    constexpr int V = DwVec<T>::V, G = kDwUnits / V;
+    constexpr int V = Vec16<T>::V, G = kDwUnits / V;
     for (int it = threadIdx.x; it < frames * 4 * G; it += 256) {
         const int gq = it % G, c = (it / G) & 3, j = it / (4 * G);
         const int t = t_first + j, u0 = ub + gq * V;
@@ -144,10 +90,10 @@ __device__ __forceinline__ void dw_stage(float *sh, int frames, int t_first, int
         for (int e = 0; e < V; ++e) h[e] = 0.f;
         if (t >= 0 && t < n && u0 < Q) {
             const size_t off = (row0 + (size_t)t) * (size_t)row + (size_t)c * comp + u0;
-            DwVec<T>::unpack(dw_load16(src + off), h);
+            Vec16<T>::unpack(load16(src + off), h);
             if (gate) {
                 float gv[V];
-                DwVec<T>::unpack(dw_load16(gate + off), gv);
+                Vec16<T>::unpack(load16(gate + off), gv);
 #pragma unroll
                 for (int e = 0; e < V; ++e) h[e] *= dw_sigmoid(gv[e]);
             }
@@ -162,7 +108,7 @@ __device__ __forceinline__ void dw_stage(float *sh, int frames, int t_first, int
 template <typename T, int KB, bool BWD>
 __global__ __launch_bounds__(256) void k_dw_conv(const DwArgs p)
 {
-    constexpr int V = DwVec<T>::V, G = kDwUnits / V;
+    constexpr int V = Vec16<T>::V, G = kDwUnits / V;
     __shared__ __attribute__((aligned(16))) float sh[(kDwTile + KB - 1) * kDwFS];
     const int b = blockIdx.z, t0 = blockIdx.x * kDwTile, ub = blockIdx.y * kDwUnits;
     const int K = p.K, Q = p.Q;
@@ -230,7 +176,7 @@ __global__ __launch_bounds__(256) void k_dw_conv(const DwArgs p)
             for (int e = 0; e < V; ++e) o[e] = src[e];
         }
         if (!BWD) {
-            dw_store16((T *)p.y + (row0 + t) * (size_t)p.yr + (size_t)c * p.yc + u0, DwVec<T>::pack(o));
+            store16((T *)p.y + (row0 + t) * (size_t)p.yr + (size_t)c * p.yc + u0, Vec16<T>::pack(o));
         } else {
             const size_t off = (row0 + t) * (size_t)p.xr + (size_t)c * p.xc + u0;
             if (p.g) {
@@ -239,8 +185,8 @@ __global__ __launch_bounds__(256) void k_dw_conv(const DwArgs p)
                 for (int e = 0; e < V; ++e) og[e] = 0.f;
                 if (on) {
                     float av[V], gv[V];
-                    DwVec<T>::unpack(dw_load16((const T *)p.a + off), av);
-                    DwVec<T>::unpack(dw_load16((const T *)p.g + off), gv);
+                    Vec16<T>::unpack(load16((const T *)p.a + off), av);
+                    Vec16<T>::unpack(load16((const T *)p.g + off), gv);
 #pragma unroll
                     for (int e = 0; e < V; ++e) {
                         const float s = dw_sigmoid(gv[e]);
@@ -248,9 +194,9 @@ __global__ __launch_bounds__(256) void k_dw_conv(const DwArgs p)
                         o[e] *= s;
                     }
                 }
-                dw_store16((T *)p.dg + off, DwVec<T>::pack(og));
+                store16((T *)p.dg + off, Vec16<T>::pack(og));
             }
-            dw_store16((T *)p.da + off, DwVec<T>::pack(o));
+            store16((T *)p.da + off, Vec16<T>::pack(o));
         }
     }
 }
@@ -452,12 +398,9 @@ __global__ __launch_bounds__(64) void k_dw_part_gen(const DwArgs p)
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-int dw_vec_width(int dtype) { return dtype == QK_F32 ? 4 : 8; }
-
 bool dw_desc_ok(const qk_qdwconv_desc_t *d, const char *what)
 {
-    if (!d) { set_error("%s: NULL descriptor", what); return false; }
-    if (d->dtype != QK_F32 && d->dtype != QK_BF16 && d->dtype != QK_F16) { set_error("%s: unknown dtype %d", what, d->dtype); return false; }
+    if (!desc_head_ok(d, what)) return false;
     if (d->batch < 1 || d->steps < 1 || d->units < 1) {
         set_error("%s: batch, steps and units must be >= 1 (got %d, %d, %d)", what, d->batch, d->steps, d->units);
         return false;
@@ -483,23 +426,13 @@ bool dw_desc_ok(const qk_qdwconv_desc_t *d, const char *what)
 
 int dw_path(const qk_qdwconv_desc_t *d)
 {
-    const int v = dw_vec_width(d->dtype);
+    const int v = vec_width(d->dtype);
     return d->units % v == 0 && d->x_row % v == 0 && d->x_comp % v == 0 && d->y_row % v == 0 && d->y_comp % v == 0
                ? QK_QDWCONV_PATH_VEC : QK_QDWCONV_PATH_GENERIC;
 }
 
 int dw_slab_rows(const qk_qdwconv_desc_t *d) { return (d->batch + kDwMaxSlabs - 1) / kDwMaxSlabs; }
 int dw_slabs(const qk_qdwconv_desc_t *d) { const int r = dw_slab_rows(d); return (d->batch + r - 1) / r; }
-
-int dw_launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return QK_OK;
-    set_error("%s: kernel launch failed: %s", what, hipGetErrorString(e));
-    return QK_ERR_LAUNCH;
-}
-
-bool dw_aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 DwArgs dw_args(const qk_qdwconv_desc_t *d)
 {
@@ -549,8 +482,7 @@ size_t qk_qdwconv_workspace_bytes(const qk_qdwconv_desc_t *desc, int32_t op)
     if (!dw_desc_ok(desc, "qk_qdwconv_workspace_bytes")) return 0;
     if (op == QK_OP_FWD) return 0;
     if (op == QK_OP_BWD) return (size_t)dw_slabs(desc) * (desc->taps + 1) * 4 * desc->units * sizeof(float);
-    set_error("qk_qdwconv_workspace_bytes: op must be QK_OP_FWD or QK_OP_BWD (got %d)", op);
-    return 0;
+    return bad_op("qk_qdwconv_workspace_bytes", op);
 }
 
 int qk_qdwconv_last_path(void) { return g_dw_path; }
@@ -561,27 +493,23 @@ int qk_qdwconv_fwd(const qk_qdwconv_desc_t *desc, const void *a, const void *g, 
     const char *what = "qk_qdwconv_fwd";
     if (!dw_desc_ok(desc, what)) return QK_ERR_INVALID_ARG;
     if (!a || !w || !y) { set_error("%s: NULL buffer", what); return QK_ERR_INVALID_ARG; }
-    const size_t es = desc->dtype == QK_F32 ? 4 : 2;
-    if (!dw_aligned(a, es) || !dw_aligned(g, es) || !dw_aligned(y, es) || !dw_aligned(w, 4) || !dw_aligned(bias, 4) || !dw_aligned(lengths, 4)) {
+    const size_t es = elem_size(desc->dtype);
+    if (!aligned(a, es) || !aligned(g, es) || !aligned(y, es) || !aligned(w, 4) || !aligned(bias, 4) || !aligned(lengths, 4)) {
         set_error("%s: misaligned buffer", what);
         return QK_ERR_INVALID_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
     DwArgs p = dw_args(desc);
     p.len = lengths; p.a = a; p.g = g; p.w = w; p.bias = bias; p.y = y;
-    const bool vec = dw_path(desc) == QK_QDWCONV_PATH_VEC && dw_aligned(a, 16) && dw_aligned(g, 16) && dw_aligned(y, 16);
+    const bool vec = dw_path(desc) == QK_QDWCONV_PATH_VEC && aligned(a, 16) && aligned(g, 16) && aligned(y, 16);
     if (vec) {
-        if (desc->dtype == QK_F32) dw_launch_conv<float, false>(p, st);
-        else if (desc->dtype == QK_BF16) dw_launch_conv<bf16, false>(p, st);
-        else dw_launch_conv<f16, false>(p, st);
+        by_dtype(desc->dtype, [&](auto t) { dw_launch_conv<decltype(t), false>(p, st); });
     } else {
         const unsigned blocks = dw_elem_blocks(p);
-        if (desc->dtype == QK_F32) hipLaunchKernelGGL((k_dw_fwd_gen<float>), dim3(blocks), dim3(256), 0, st, p);
-        else if (desc->dtype == QK_BF16) hipLaunchKernelGGL((k_dw_fwd_gen<bf16>), dim3(blocks), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_dw_fwd_gen<f16>), dim3(blocks), dim3(256), 0, st, p);
+        by_dtype(desc->dtype, [&](auto t) { hipLaunchKernelGGL((k_dw_fwd_gen<decltype(t)>), dim3(blocks), dim3(256), 0, st, p); });
     }
     g_dw_path = vec ? QK_QDWCONV_PATH_VEC : QK_QDWCONV_PATH_GENERIC;
-    return dw_launched(what);
+    return launched(what);
 }
 
 int qk_qdwconv_bwd(const qk_qdwconv_desc_t *desc, const void *dy, const void *a, const void *g, const float *w,
@@ -592,38 +520,33 @@ int qk_qdwconv_bwd(const qk_qdwconv_desc_t *desc, const void *dy, const void *a,
     if (!dw_desc_ok(desc, what)) return QK_ERR_INVALID_ARG;
     if (!dy || !a || !w || !da) { set_error("%s: NULL buffer", what); return QK_ERR_INVALID_ARG; }
     if ((g == nullptr) != (dg == nullptr)) { set_error("%s: g and dg must both be given or both be NULL", what); return QK_ERR_INVALID_ARG; }
-    const size_t es = desc->dtype == QK_F32 ? 4 : 2;
-    if (!dw_aligned(dy, es) || !dw_aligned(a, es) || !dw_aligned(g, es) || !dw_aligned(da, es) || !dw_aligned(dg, es) || !dw_aligned(w, 4)
-        || !dw_aligned(lengths, 4) || !dw_aligned(dw, 4) || !dw_aligned(dbias, 4) || !dw_aligned(workspace, 16)) {
+    const size_t es = elem_size(desc->dtype);
+    if (!aligned(dy, es) || !aligned(a, es) || !aligned(g, es) || !aligned(da, es) || !aligned(dg, es) || !aligned(w, 4)
+        || !aligned(lengths, 4) || !aligned(dw, 4) || !aligned(dbias, 4) || !aligned(workspace, 16)) {
         set_error("%s: misaligned buffer (16 bytes for the workspace)", what);
         return QK_ERR_INVALID_ARG;
     }
     const bool wg = dw || dbias;
     const size_t need = wg ? qk_qdwconv_workspace_bytes(desc, QK_OP_BWD) : 0;
-    if (wg && (!workspace || workspace_bytes < need)) { set_error("%s: workspace of %zu bytes needed, %zu given", what, need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    if (wg && workspace_ok(what, workspace, workspace_bytes, need) != QK_OK) return QK_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     DwArgs p = dw_args(desc);
     p.len = lengths; p.dy = dy; p.a = a; p.g = g; p.w = w; p.da = da; p.dg = dg; p.part = wg ? (float *)workspace : nullptr;
     const int slabs = dw_slabs(desc);
-    const bool vec = dw_path(desc) == QK_QDWCONV_PATH_VEC && dw_aligned(dy, 16) && dw_aligned(a, 16) && dw_aligned(g, 16) && dw_aligned(da, 16)
-                     && dw_aligned(dg, 16);
+    const bool vec = dw_path(desc) == QK_QDWCONV_PATH_VEC && aligned(dy, 16) && aligned(a, 16) && aligned(g, 16) && aligned(da, 16)
+                     && aligned(dg, 16);
     if (vec) {
-        if (desc->dtype == QK_F32) { dw_launch_conv<float, true>(p, st); if (wg) dw_launch_wgrad<float>(p, slabs, st); }
-        else if (desc->dtype == QK_BF16) { dw_launch_conv<bf16, true>(p, st); if (wg) dw_launch_wgrad<bf16>(p, slabs, st); }
-        else { dw_launch_conv<f16, true>(p, st); if (wg) dw_launch_wgrad<f16>(p, slabs, st); }
+        by_dtype(desc->dtype, [&](auto t) {
+            dw_launch_conv<decltype(t), true>(p, st);
+            if (wg) dw_launch_wgrad<decltype(t)>(p, slabs, st);
+        });
     } else {
         const unsigned blocks = dw_elem_blocks(p);
         const dim3 pgrid((unsigned)((desc->units + 63) / 64), (unsigned)(desc->taps + 1), (unsigned)slabs);
-        if (desc->dtype == QK_F32) {
-            hipLaunchKernelGGL((k_dw_bwd_gen<float>), dim3(blocks), dim3(256), 0, st, p);
-            if (wg) hipLaunchKernelGGL((k_dw_part_gen<float>), pgrid, dim3(64), 0, st, p);
-        } else if (desc->dtype == QK_BF16) {
-            hipLaunchKernelGGL((k_dw_bwd_gen<bf16>), dim3(blocks), dim3(256), 0, st, p);
-            if (wg) hipLaunchKernelGGL((k_dw_part_gen<bf16>), pgrid, dim3(64), 0, st, p);
-        } else {
-            hipLaunchKernelGGL((k_dw_bwd_gen<f16>), dim3(blocks), dim3(256), 0, st, p);
-            if (wg) hipLaunchKernelGGL((k_dw_part_gen<f16>), pgrid, dim3(64), 0, st, p);
-        }
+        by_dtype(desc->dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_dw_bwd_gen<decltype(t)>), dim3(blocks), dim3(256), 0, st, p);
+            if (wg) hipLaunchKernelGGL((k_dw_part_gen<decltype(t)>), pgrid, dim3(64), 0, st, p);
+        });
     }
     if (wg) {
         const int cols = (desc->taps + 1) * 4 * desc->units;
@@ -631,7 +554,7 @@ int qk_qdwconv_bwd(const qk_qdwconv_desc_t *desc, const void *dy, const void *a,
                            desc->units, dw, dbias);
     }
     g_dw_path = vec ? QK_QDWCONV_PATH_VEC : QK_QDWCONV_PATH_GENERIC;
-    return dw_launched(what);
+    return launched(what);
 }
 
 }  // extern "C"

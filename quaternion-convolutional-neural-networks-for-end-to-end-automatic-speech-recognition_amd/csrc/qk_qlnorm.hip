@@ -14,6 +14,7 @@
 // three (backward: two) passes over the row, the second and third served by the cache; the weight-gradient partials of a slab by
 // a thread per unit.  Correct before fast.
 #include "qk_common.h"
+#include "qk_seq.h"
 #include "../../include/qk_norm.h"
 
 #include <math.h>
@@ -24,58 +25,6 @@ namespace {
 constexpr int kQnMaxQ = 1024;          // widest row the vector kernels keep in registers
 constexpr int kQnSlabTarget = 768;     // slabs aimed at for large inputs: three resident workgroups (the backward's registers) on each of 256 CUs
 constexpr int kQnSlabMin = 16;         // rows per slab at least (a multiple of the four waves)
-
-typedef _Float16 qn_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 qn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float qn_f32x8 __attribute__((ext_vector_type(8)));
-
-// V activation elements in one 16-byte register group
-template <typename T> struct QnVec;
-template <> struct QnVec<float> {
-    static constexpr int V = 4;
-    static __device__ __forceinline__ void unpack(const uint4 &r, float (&o)[4])
-    {
-        o[0] = __uint_as_float(r.x); o[1] = __uint_as_float(r.y); o[2] = __uint_as_float(r.z); o[3] = __uint_as_float(r.w);
-    }
-    static __device__ __forceinline__ uint4 pack(const float (&v)[4])
-    {
-        return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
-    }
-};
-template <> struct QnVec<bf16> {
-    static constexpr int V = 8;
-    static __device__ __forceinline__ void unpack(const uint4 &r, float (&o)[8])
-    {
-        const unsigned w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { o[2 * i] = __uint_as_float(w[i] << 16); o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-    }
-    static __device__ __forceinline__ uint4 pack(const float (&v)[8])
-    {
-        // round-to-nearest-even by the packed conversion instruction of gfx950 (the integer form of from_f32<bf16> is ~6 VALU
-        // operations per element, a fifth of the backward's arithmetic)
-        qn_f32x8 f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) f[i] = v[i];
-        return __builtin_bit_cast(uint4, __builtin_convertvector(f, qn_bf16x8));
-    }
-};
-template <> struct QnVec<f16> {
-    static constexpr int V = 8;
-    static __device__ __forceinline__ void unpack(const uint4 &r, float (&o)[8])
-    {
-        const qn_f16x8 h = __builtin_bit_cast(qn_f16x8, r);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (float)h[i];
-    }
-    static __device__ __forceinline__ uint4 pack(const float (&v)[8])
-    {
-        qn_f16x8 h;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) h[i] = (f16)v[i];
-        return __builtin_bit_cast(uint4, h);
-    }
-};
 
 // v + (v of the lane a DPP control names); every lane is active and every source lane exists
 template <int CTRL>
@@ -130,16 +79,11 @@ __device__ __forceinline__ bool qn_active(const int *len, int steps, int row)
     return row - b * steps < len[b];
 }
 
-template <typename T>
-__device__ __forceinline__ void qn_store16(T *p, const uint4 &v) { *reinterpret_cast<uint4 *>(p) = v; }
-template <typename T>
-__device__ __forceinline__ uint4 qn_load16(const T *p) { return *reinterpret_cast<const uint4 *>(p); }
-
 // ---- vector forward ---------------------------------------------------------------------------------------------------------------
 template <typename T, int P>
 __global__ __launch_bounds__(256) void k_qln_fwd(const QnFwd a)
 {
-    constexpr int V = QnVec<T>::V;
+    constexpr int V = Vec16<T>::V;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int Q = a.Q;
@@ -177,7 +121,7 @@ __global__ __launch_bounds__(256) void k_qln_fwd(const QnFwd a)
             for (int p = 0; p < P; ++p)
                 if (ok[p]) {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) qn_store16(yr + c * Q + (lane + 64 * p) * V, make_uint4(0u, 0u, 0u, 0u));
+                    for (int c = 0; c < 4; ++c) store16(yr + c * Q + (lane + 64 * p) * V, make_uint4(0u, 0u, 0u, 0u));
                 }
             if (lane < 5) st[lane] = 0.f;
             continue;
@@ -189,8 +133,8 @@ __global__ __launch_bounds__(256) void k_qln_fwd(const QnFwd a)
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 uint4 raw = make_uint4(0u, 0u, 0u, 0u);
-                if (ok[p]) raw = qn_load16(xr + c * Q + (lane + 64 * p) * V);
-                QnVec<T>::unpack(raw, v[p][c]);
+                if (ok[p]) raw = load16(xr + c * Q + (lane + 64 * p) * V);
+                Vec16<T>::unpack(raw, v[p][c]);
             }
         }
         // the means, relative to the row's first unit (lane 0, group 0 always holds it)
@@ -231,7 +175,7 @@ __global__ __launch_bounds__(256) void k_qln_fwd(const QnFwd a)
                     float o[V];
 #pragma unroll
                     for (int e = 0; e < V; ++e) o[e] = gm[p][e] * (v[p][c][e] * rstd) + bt[p][c][e];
-                    qn_store16(yr + c * Q + (lane + 64 * p) * V, QnVec<T>::pack(o));
+                    store16(yr + c * Q + (lane + 64 * p) * V, Vec16<T>::pack(o));
                 }
             }
         }
@@ -248,7 +192,7 @@ __global__ __launch_bounds__(256) void k_qln_fwd(const QnFwd a)
 template <typename T, int P, bool WG>
 __global__ __launch_bounds__(256) void k_qln_bwd(const QnBwd a)
 {
-    constexpr int V = QnVec<T>::V;
+    constexpr int V = Vec16<T>::V;
     __shared__ float red[3][V][64];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -281,7 +225,7 @@ __global__ __launch_bounds__(256) void k_qln_bwd(const QnBwd a)
             for (int p = 0; p < P; ++p)
                 if (ok[p]) {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) qn_store16(dxr + c * Q + (lane + 64 * p) * V, make_uint4(0u, 0u, 0u, 0u));
+                    for (int c = 0; c < 4; ++c) store16(dxr + c * Q + (lane + 64 * p) * V, make_uint4(0u, 0u, 0u, 0u));
                 }
             continue;
         }
@@ -294,8 +238,8 @@ __global__ __launch_bounds__(256) void k_qln_bwd(const QnBwd a)
             for (int c = 0; c < 4; ++c) {
                 xraw[p][c] = draw[p][c] = make_uint4(0u, 0u, 0u, 0u);
                 if (ok[p]) {
-                    xraw[p][c] = qn_load16(xr + c * Q + (lane + 64 * p) * V);
-                    draw[p][c] = qn_load16(dyr + c * Q + (lane + 64 * p) * V);
+                    xraw[p][c] = load16(xr + c * Q + (lane + 64 * p) * V);
+                    draw[p][c] = load16(dyr + c * Q + (lane + 64 * p) * V);
                 }
             }
         }
@@ -307,8 +251,8 @@ __global__ __launch_bounds__(256) void k_qln_bwd(const QnBwd a)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     float xv[V], dv[V];
-                    QnVec<T>::unpack(xraw[p][c], xv);
-                    QnVec<T>::unpack(draw[p][c], dv);
+                    Vec16<T>::unpack(xraw[p][c], xv);
+                    Vec16<T>::unpack(draw[p][c], dv);
 #pragma unroll
                     for (int e = 0; e < V; ++e) {
                         const float t = dv[e] * ((xv[e] - mu[c]) * rstd);          // dy xhat
@@ -331,12 +275,12 @@ __global__ __launch_bounds__(256) void k_qln_bwd(const QnBwd a)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     float xv[V], dv[V], o[V];
-                    QnVec<T>::unpack(xraw[p][c], xv);
-                    QnVec<T>::unpack(draw[p][c], dv);
+                    Vec16<T>::unpack(xraw[p][c], xv);
+                    Vec16<T>::unpack(draw[p][c], dv);
                     const float mr = sum[c] * inv_q * rstd;
 #pragma unroll
                     for (int e = 0; e < V; ++e) o[e] = fmaf(-((xv[e] - mu[c]) * rstd), sr, fmaf(dv[e], gr[e], -mr));
-                    qn_store16(dxr + c * Q + (lane + 64 * p) * V, QnVec<T>::pack(o));
+                    store16(dxr + c * Q + (lane + 64 * p) * V, Vec16<T>::pack(o));
                 }
             }
         }
@@ -547,12 +491,9 @@ __global__ __launch_bounds__(256) void k_qln_part_gen(const QnBwd a)
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-int qn_vec_width(int dtype) { return dtype == QK_F32 ? 4 : 8; }
-
 bool qn_desc_ok(const qk_qlnorm_desc_t *d, const char *what)
 {
-    if (!d) { set_error("%s: NULL descriptor", what); return false; }
-    if (d->dtype != QK_F32 && d->dtype != QK_BF16 && d->dtype != QK_F16) { set_error("%s: unknown dtype %d", what, d->dtype); return false; }
+    if (!desc_head_ok(d, what)) return false;
     if (d->rows < 1 || d->q < 1) { set_error("%s: rows and q must be >= 1 (got %d, %d)", what, d->rows, d->q); return false; }
     if (d->q > (1 << 26) || d->rows > (1 << 30)) { set_error("%s: shape out of range (rows %d, q %d)", what, d->rows, d->q); return false; }
     if (d->steps < 0 || (d->steps > 0 && d->rows % d->steps != 0)) {
@@ -569,7 +510,7 @@ bool qn_desc_ok(const qk_qlnorm_desc_t *d, const char *what)
 
 int qn_path(const qk_qlnorm_desc_t *d)
 {
-    const int v = qn_vec_width(d->dtype);
+    const int v = vec_width(d->dtype);
     return d->q % v == 0 && d->q <= kQnMaxQ && d->x_stride % v == 0 && d->y_stride % v == 0 ? QK_QLNORM_PATH_VEC : QK_QLNORM_PATH_GENERIC;
 }
 
@@ -580,20 +521,11 @@ int qn_slab_rows(const qk_qlnorm_desc_t *d)
 }
 int qn_slabs(const qk_qlnorm_desc_t *d) { const int sr = qn_slab_rows(d); return (d->rows + sr - 1) / sr; }
 
-int qn_launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return QK_OK;
-    set_error("%s: kernel launch failed: %s", what, hipGetErrorString(e));
-    return QK_ERR_LAUNCH;
-}
-
-bool qn_aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 int qn_row_grid(int rows, int cap) { const int g = (rows + 3) / 4; return g < cap ? g : cap; }
 // register groups per lane of the vector kernels: 1, 2 or 4
 int qn_groups(const qk_qlnorm_desc_t *d)
 {
-    const int need = (d->q + 64 * qn_vec_width(d->dtype) - 1) / (64 * qn_vec_width(d->dtype));
+    const int need = (d->q + 64 * vec_width(d->dtype) - 1) / (64 * vec_width(d->dtype));
     return need <= 1 ? 1 : need <= 2 ? 2 : 4;
 }
 
@@ -635,8 +567,7 @@ size_t qk_qlnorm_workspace_bytes(const qk_qlnorm_desc_t *desc, int32_t op)
     if (!qn_desc_ok(desc, "qk_qlnorm_workspace_bytes")) return 0;
     if (op == QK_OP_FWD) return 0;
     if (op == QK_OP_BWD) return (size_t)qn_slabs(desc) * 5 * desc->q * sizeof(float);
-    set_error("qk_qlnorm_workspace_bytes: op must be QK_OP_FWD or QK_OP_BWD (got %d)", op);
-    return 0;
+    return bad_op("qk_qlnorm_workspace_bytes", op);
 }
 
 int qk_qlnorm_fwd(const qk_qlnorm_desc_t *desc, const void *x, const float *gamma, const float *beta, const int32_t *lengths,
@@ -647,8 +578,8 @@ int qk_qlnorm_fwd(const qk_qlnorm_desc_t *desc, const void *x, const float *gamm
     if (!x || !y || !stats) { set_error("%s: NULL buffer", what); return QK_ERR_INVALID_ARG; }
     if (lengths && desc->steps == 0) { set_error("%s: lengths given with steps == 0", what); return QK_ERR_INVALID_ARG; }
     if (!(epsilon >= 0.f)) { set_error("%s: epsilon must be >= 0", what); return QK_ERR_INVALID_ARG; }
-    const size_t es = desc->dtype == QK_F32 ? 4 : 2;
-    if (!qn_aligned(x, es) || !qn_aligned(y, es) || !qn_aligned(gamma, 4) || !qn_aligned(beta, 4) || !qn_aligned(stats, 4) || !qn_aligned(lengths, 4)) {
+    const size_t es = elem_size(desc->dtype);
+    if (!aligned(x, es) || !aligned(y, es) || !aligned(gamma, 4) || !aligned(beta, 4) || !aligned(stats, 4) || !aligned(lengths, 4)) {
         set_error("%s: misaligned buffer", what);
         return QK_ERR_INVALID_ARG;
     }
@@ -656,19 +587,15 @@ int qk_qlnorm_fwd(const qk_qlnorm_desc_t *desc, const void *x, const float *gamm
     QnFwd a;
     a.rows = desc->rows; a.steps = desc->steps; a.Q = desc->q; a.xs = desc->x_stride; a.ys = desc->y_stride; a.eps = epsilon;
     a.len = lengths; a.x = x; a.gamma = gamma; a.beta = beta; a.y = y; a.stats = stats;
-    const bool vec = qn_path(desc) == QK_QLNORM_PATH_VEC && qn_aligned(x, 16) && qn_aligned(y, 16) && qn_aligned(gamma, 16) && qn_aligned(beta, 16);
+    const bool vec = qn_path(desc) == QK_QLNORM_PATH_VEC && aligned(x, 16) && aligned(y, 16) && aligned(gamma, 16) && aligned(beta, 16);
     if (vec) {
         const int grid = qn_row_grid(desc->rows, 1024), groups = qn_groups(desc);
-        if (desc->dtype == QK_F32) qn_launch_fwd_vec<float>(groups, grid, a, st);
-        else if (desc->dtype == QK_BF16) qn_launch_fwd_vec<bf16>(groups, grid, a, st);
-        else qn_launch_fwd_vec<f16>(groups, grid, a, st);
+        by_dtype(desc->dtype, [&](auto t) { qn_launch_fwd_vec<decltype(t)>(groups, grid, a, st); });
     } else {
         const int grid = qn_row_grid(desc->rows, 2048);
-        if (desc->dtype == QK_F32) hipLaunchKernelGGL((k_qln_fwd_gen<float>), dim3(grid), dim3(256), 0, st, a);
-        else if (desc->dtype == QK_BF16) hipLaunchKernelGGL((k_qln_fwd_gen<bf16>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_qln_fwd_gen<f16>), dim3(grid), dim3(256), 0, st, a);
+        by_dtype(desc->dtype, [&](auto t) { hipLaunchKernelGGL((k_qln_fwd_gen<decltype(t)>), dim3(grid), dim3(256), 0, st, a); });
     }
-    return qn_launched(what);
+    return launched(what);
 }
 
 int qk_qlnorm_bwd(const qk_qlnorm_desc_t *desc, const void *dy, const void *x, const float *gamma, const int32_t *lengths,
@@ -678,52 +605,41 @@ int qk_qlnorm_bwd(const qk_qlnorm_desc_t *desc, const void *dy, const void *x, c
     if (!qn_desc_ok(desc, what)) return QK_ERR_INVALID_ARG;
     if (!dy || !x || !stats || !dx) { set_error("%s: NULL buffer", what); return QK_ERR_INVALID_ARG; }
     if (lengths && desc->steps == 0) { set_error("%s: lengths given with steps == 0", what); return QK_ERR_INVALID_ARG; }
-    const size_t es = desc->dtype == QK_F32 ? 4 : 2;
-    if (!qn_aligned(x, es) || !qn_aligned(dy, es) || !qn_aligned(dx, es) || !qn_aligned(gamma, 4) || !qn_aligned(stats, 4) || !qn_aligned(lengths, 4)
-        || !qn_aligned(dgamma, 4) || !qn_aligned(dbeta, 4) || !qn_aligned(workspace, 16)) {
+    const size_t es = elem_size(desc->dtype);
+    if (!aligned(x, es) || !aligned(dy, es) || !aligned(dx, es) || !aligned(gamma, 4) || !aligned(stats, 4) || !aligned(lengths, 4)
+        || !aligned(dgamma, 4) || !aligned(dbeta, 4) || !aligned(workspace, 16)) {
         set_error("%s: misaligned buffer (16 bytes for the workspace)", what);
         return QK_ERR_INVALID_ARG;
     }
     const bool wg = dgamma || dbeta;
     const size_t need = wg ? qk_qlnorm_workspace_bytes(desc, QK_OP_BWD) : 0;
-    if (wg && (!workspace || workspace_bytes < need)) { set_error("%s: workspace of %zu bytes needed, %zu given", what, need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    if (wg && workspace_ok(what, workspace, workspace_bytes, need) != QK_OK) return QK_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     QnBwd a;
     a.rows = desc->rows; a.steps = desc->steps; a.Q = desc->q; a.xs = desc->x_stride; a.ys = desc->y_stride; a.slab_rows = qn_slab_rows(desc);
     a.len = lengths; a.dy = dy; a.x = x; a.gamma = gamma; a.stats = stats; a.dx = dx; a.part = wg ? (float *)workspace : nullptr;
     const int slabs = qn_slabs(desc);
-    const bool vec = qn_path(desc) == QK_QLNORM_PATH_VEC && qn_aligned(x, 16) && qn_aligned(dy, 16) && qn_aligned(dx, 16) && qn_aligned(gamma, 16);
+    const bool vec = qn_path(desc) == QK_QLNORM_PATH_VEC && aligned(x, 16) && aligned(dy, 16) && aligned(dx, 16) && aligned(gamma, 16);
     if (vec) {
         const int groups = qn_groups(desc);
-        if (wg) {
-            if (desc->dtype == QK_F32) qn_launch_bwd_vec<float, true>(groups, slabs, a, st);
-            else if (desc->dtype == QK_BF16) qn_launch_bwd_vec<bf16, true>(groups, slabs, a, st);
-            else qn_launch_bwd_vec<f16, true>(groups, slabs, a, st);
-        } else {
-            if (desc->dtype == QK_F32) qn_launch_bwd_vec<float, false>(groups, slabs, a, st);
-            else if (desc->dtype == QK_BF16) qn_launch_bwd_vec<bf16, false>(groups, slabs, a, st);
-            else qn_launch_bwd_vec<f16, false>(groups, slabs, a, st);
-        }
+        by_dtype(desc->dtype, [&](auto t) {
+            if (wg) qn_launch_bwd_vec<decltype(t), true>(groups, slabs, a, st);
+            else qn_launch_bwd_vec<decltype(t), false>(groups, slabs, a, st);
+        });
     } else {
         const int grid = qn_row_grid(desc->rows, 2048);
         const dim3 pgrid((unsigned)((desc->q + 255) / 256), (unsigned)slabs);
-        if (desc->dtype == QK_F32) {
-            hipLaunchKernelGGL((k_qln_bwd_gen<float>), dim3(grid), dim3(256), 0, st, a);
-            if (wg) hipLaunchKernelGGL((k_qln_part_gen<float>), pgrid, dim3(256), 0, st, a);
-        } else if (desc->dtype == QK_BF16) {
-            hipLaunchKernelGGL((k_qln_bwd_gen<bf16>), dim3(grid), dim3(256), 0, st, a);
-            if (wg) hipLaunchKernelGGL((k_qln_part_gen<bf16>), pgrid, dim3(256), 0, st, a);
-        } else {
-            hipLaunchKernelGGL((k_qln_bwd_gen<f16>), dim3(grid), dim3(256), 0, st, a);
-            if (wg) hipLaunchKernelGGL((k_qln_part_gen<f16>), pgrid, dim3(256), 0, st, a);
-        }
+        by_dtype(desc->dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_qln_bwd_gen<decltype(t)>), dim3(grid), dim3(256), 0, st, a);
+            if (wg) hipLaunchKernelGGL((k_qln_part_gen<decltype(t)>), pgrid, dim3(256), 0, st, a);
+        });
     }
     if (wg) {
         const int blocks = (5 * desc->q + 63) / 64;
         if (desc->q % 4 == 0) hipLaunchKernelGGL((k_qln_reduce<4>), dim3(blocks), dim3(1024), 0, st, (const float *)workspace, slabs, desc->q, dgamma, dbeta);
         else hipLaunchKernelGGL((k_qln_reduce<1>), dim3(blocks), dim3(1024), 0, st, (const float *)workspace, slabs, desc->q, dgamma, dbeta);
     }
-    return qn_launched(what);
+    return launched(what);
 }
 
 }  // extern "C"

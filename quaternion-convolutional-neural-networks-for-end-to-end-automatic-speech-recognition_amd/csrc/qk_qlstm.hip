@@ -19,6 +19,7 @@
 // h has two state buffers (every workgroup reads all of h_{t-1} while others write h_t); c, the dh carry and dc are updated in
 // place by the lane that owns the element.  dz_t is written to dzx[:, t] and read from there by the next launch.
 #include "qk_common.h"
+#include "qk_seq.h"
 #include "../../include/qk_rnn.h"
 
 #include <math.h>
@@ -26,17 +27,6 @@
 namespace qk {
 namespace {
 
-typedef __bf16 ql_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ql_f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ floatx4 ql_mfma(bf16, const uint4 &a, const uint4 &b, const floatx4 &c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(ql_bf16x8, a), __builtin_bit_cast(ql_bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ floatx4 ql_mfma(f16, const uint4 &a, const uint4 &b, const floatx4 &c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ql_f16x8, a), __builtin_bit_cast(ql_f16x8, b), c, 0, 0, 0);
-}
 // both 16-bit formats keep the sign in bit 15
 __device__ __forceinline__ uint4 ql_neg(const uint4 &v)
 {
@@ -44,7 +34,6 @@ __device__ __forceinline__ uint4 ql_neg(const uint4 &v)
 }
 // sign of the product of gathered component a with compact part a ^ b in produced component b (the dense table)
 __device__ __forceinline__ constexpr bool ql_minus(int a, int b) { return (kSignConj >> (a * 4 + b)) & 1u; }
-template <typename T> __device__ __forceinline__ float ql_round(float v) { return to_f32(from_f32<T>(v)); }
 __device__ __forceinline__ float ql_sigmoid(float z) { return 1.f / (1.f + expf(-z)); }
 
 struct QlFwd {
@@ -154,8 +143,6 @@ __device__ __forceinline__ void ql_cell_bwd(const QlBwd &a, int d, bool rev, int
     a.dc[st] = dct * gf;
 }
 
-__device__ __forceinline__ uint4 ql_ld16(const void *p) { return *reinterpret_cast<const uint4 *>(p); }
-
 // ---- matrix-core kernels: 256 threads, blockIdx = (unit slice of 16, row tile of 16, direction) --------------------------------------
 inline int ql_ksteps(int Q) { return (Q + 31) / 32; }
 
@@ -184,7 +171,7 @@ __global__ __launch_bounds__(256) void k_ql_fwd16(const QlFwd a)
             const bool kv = k < Q;                       // Q % 32 == 16: the upper half of the last K step is empty (zeros in the image)
             uint4 af[4], nf[4], bf[16];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) af[c] = kv ? ql_ld16(h + c * Q + k) : zero;
+            for (int c = 0; c < 4; ++c) af[c] = kv ? load16(h + c * Q + k) : zero;
 #pragma unroll
             for (int f = 0; f < 16; ++f) bf[f] = w[(ks * 16 + f) * 64];
             // all 20 loads of the K step are in flight before the first product waits for one: left alone, the scheduler keeps two
@@ -199,7 +186,7 @@ __global__ __launch_bounds__(256) void k_ql_fwd16(const QlFwd a)
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const int b = c ^ p;
-                        acc[b][g] = ql_mfma(T(), ql_minus(c, b) ? nf[c] : af[c], bf[p * 4 + g], acc[b][g]);
+                        acc[b][g] = mfma16(T(), ql_minus(c, b) ? nf[c] : af[c], bf[p * 4 + g], acc[b][g]);
                     }
         }
     }
@@ -251,8 +238,8 @@ __global__ __launch_bounds__(256) void k_ql_bwd16(const QlBwd a)
                 const bool jv = j0 + 128 * h < U;        // wave-uniform
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
-                    af[h][b] = jv ? ql_ld16(dz + b * U + j) : zero;
-                    bf[h][b] = jv ? ql_ld16(w + b * U + j) : zero;
+                    af[h][b] = jv ? load16(dz + b * U + j) : zero;
+                    bf[h][b] = jv ? load16(w + b * U + j) : zero;
                 }
             }
             __builtin_amdgcn_sched_barrier(0);           // (as in the forward: no product in front of the last load)
@@ -265,7 +252,7 @@ __global__ __launch_bounds__(256) void k_ql_bwd16(const QlBwd a)
 #pragma unroll
                     for (int p = 0; p < 4; ++p) {
                         const int b = c ^ p;
-                        acc[c] = ql_mfma(T(), ql_minus(c, b) ? nf[h][b] : af[h][b], bf[h][p], acc[c]);
+                        acc[c] = mfma16(T(), ql_minus(c, b) ? nf[h][b] : af[h][b], bf[h][p], acc[c]);
                     }
             }
         }
@@ -306,7 +293,7 @@ __global__ __launch_bounds__(256) void k_ql_fwd_gen(const QlFwd a)
                 const float hv = sg * to_f32(h[g4 * Q + k]);
                 const float *rr = rp + (long long)k * 4 * U;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) zr[g] += hv * ql_round<T>(rr[g * Q]);
+                for (int g = 0; g < 4; ++g) zr[g] += hv * round_to<T>(rr[g * Q]);
             }
         }
     }
@@ -332,7 +319,7 @@ __global__ __launch_bounds__(256) void k_ql_bwd_gen(const QlBwd a)
             const T *dzb = dz + pb * U;
             const float *rr = R + (c ^ pb) * U;
             float s = 0.f;
-            for (int j = 0; j < U; ++j) s += to_f32(dzb[j]) * ql_round<T>(rr[j]);
+            for (int j = 0; j < U; ++j) s += to_f32(dzb[j]) * round_to<T>(rr[j]);
             dh += sg * s;
         }
     }
@@ -365,13 +352,9 @@ __global__ __launch_bounds__(256) void k_ql_prep(const float *R, T *out, int Q, 
     }
 }
 
-size_t ql_align(size_t n) { return (n + 255) / 256 * 256; }
-size_t ql_esize(int dtype) { return dtype == QK_F32 ? 4 : 2; }
-
 bool ql_desc_ok(const qk_qlstm_desc_t *d, const char *what)
 {
-    if (!d) { set_error("%s: NULL descriptor", what); return false; }
-    if (d->dtype != QK_F32 && d->dtype != QK_BF16 && d->dtype != QK_F16) { set_error("%s: unknown dtype %d", what, d->dtype); return false; }
+    if (!desc_head_ok(d, what)) return false;
     if (d->batch < 1 || d->steps < 1 || d->q_units < 1) {
         set_error("%s: batch, steps and q_units must be >= 1 (got %d, %d, %d)", what, d->batch, d->steps, d->q_units);
         return false;
@@ -399,19 +382,9 @@ size_t ql_image_elems(const qk_qlstm_desc_t *d, bool fwd)
 }
 size_t ql_image_bytes(const qk_qlstm_desc_t *d, bool fwd)
 {
-    return ql_path(d) == QK_QLSTM_PATH_MFMA16 ? ql_align(ql_image_elems(d, fwd) * 2) : 0;
+    return ql_path(d) == QK_QLSTM_PATH_MFMA16 ? align256(ql_image_elems(d, fwd) * 2) : 0;
 }
 size_t ql_state_elems(const qk_qlstm_desc_t *d) { return (size_t)d->directions * d->batch * 4 * d->q_units; }
-
-int ql_launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return QK_OK;
-    set_error("%s: kernel launch failed: %s", what, hipGetErrorString(e));
-    return QK_ERR_LAUNCH;
-}
-
-bool ql_aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 template <typename T>
 void ql_launch_prep(const float *R, void *out, const qk_qlstm_desc_t *d, int fragments, hipStream_t st)
@@ -430,14 +403,11 @@ void ql_launch_step<QlFwd>(const qk_qlstm_desc_t *d, bool, const QlFwd &a, hipSt
     const int Q = d->q_units, B = d->batch, D = d->directions;
     if (ql_path(d) == QK_QLSTM_PATH_MFMA16) {
         const dim3 grid(Q / 16, (B + 15) / 16, D);
-        if (d->dtype == QK_BF16) hipLaunchKernelGGL((k_ql_fwd16<bf16>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_ql_fwd16<f16>), grid, dim3(256), 0, st, a);
+        by_dtype16(d->dtype, [&](auto t) { hipLaunchKernelGGL((k_ql_fwd16<decltype(t)>), grid, dim3(256), 0, st, a); });
         return;
     }
     const dim3 grid((unsigned)(((long long)B * 4 * Q + 255) / 256), 1, D);
-    if (d->dtype == QK_F32) hipLaunchKernelGGL((k_ql_fwd_gen<float>), grid, dim3(256), 0, st, a);
-    else if (d->dtype == QK_BF16) hipLaunchKernelGGL((k_ql_fwd_gen<bf16>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_ql_fwd_gen<f16>), grid, dim3(256), 0, st, a);
+    by_dtype(d->dtype, [&](auto t) { hipLaunchKernelGGL((k_ql_fwd_gen<decltype(t)>), grid, dim3(256), 0, st, a); });
 }
 
 template <>
@@ -446,14 +416,11 @@ void ql_launch_step<QlBwd>(const qk_qlstm_desc_t *d, bool, const QlBwd &a, hipSt
     const int Q = d->q_units, B = d->batch, D = d->directions;
     if (ql_path(d) == QK_QLSTM_PATH_MFMA16) {
         const dim3 grid(Q / 16, (B + 15) / 16, D);
-        if (d->dtype == QK_BF16) hipLaunchKernelGGL((k_ql_bwd16<bf16>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_ql_bwd16<f16>), grid, dim3(256), 0, st, a);
+        by_dtype16(d->dtype, [&](auto t) { hipLaunchKernelGGL((k_ql_bwd16<decltype(t)>), grid, dim3(256), 0, st, a); });
         return;
     }
     const dim3 grid((unsigned)(((long long)B * 4 * Q + 255) / 256), 1, D);
-    if (d->dtype == QK_F32) hipLaunchKernelGGL((k_ql_bwd_gen<float>), grid, dim3(256), 0, st, a);
-    else if (d->dtype == QK_BF16) hipLaunchKernelGGL((k_ql_bwd_gen<bf16>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_ql_bwd_gen<f16>), grid, dim3(256), 0, st, a);
+    by_dtype(d->dtype, [&](auto t) { hipLaunchKernelGGL((k_ql_bwd_gen<decltype(t)>), grid, dim3(256), 0, st, a); });
 }
 
 }  // namespace
@@ -471,10 +438,9 @@ int qk_qlstm_supported(const qk_qlstm_desc_t *desc)
 size_t qk_qlstm_workspace_bytes(const qk_qlstm_desc_t *desc, int32_t op)
 {
     if (!ql_desc_ok(desc, "qk_qlstm_workspace_bytes")) return 0;
-    if (op == QK_OP_FWD) return ql_image_bytes(desc, true) + 2 * ql_align(ql_state_elems(desc) * ql_esize(desc->dtype));
-    if (op == QK_OP_BWD) return ql_image_bytes(desc, false) + ql_align(ql_state_elems(desc) * 4);
-    set_error("qk_qlstm_workspace_bytes: op must be QK_OP_FWD or QK_OP_BWD (got %d)", op);
-    return 0;
+    if (op == QK_OP_FWD) return ql_image_bytes(desc, true) + 2 * align256(ql_state_elems(desc) * elem_size(desc->dtype));
+    if (op == QK_OP_BWD) return ql_image_bytes(desc, false) + align256(ql_state_elems(desc) * 4);
+    return bad_op("qk_qlstm_workspace_bytes", op);
 }
 
 size_t qk_qlstm_reserve_bytes(const qk_qlstm_desc_t *desc)
@@ -489,21 +455,18 @@ int qk_qlstm_fwd(const qk_qlstm_desc_t *desc, const void *zx, const float *R, co
     const char *what = "qk_qlstm_fwd";
     if (!ql_desc_ok(desc, what)) return QK_ERR_INVALID_ARG;
     if (!zx || !R || !y || !hT || !cT || !reserve) { set_error("%s: NULL buffer", what); return QK_ERR_INVALID_ARG; }
-    if (!ql_aligned(zx, 16) || !ql_aligned(h0, 16) || !ql_aligned(y, 16) || !ql_aligned(hT, 16) || !ql_aligned(workspace, 16) || !ql_aligned(R, 4)
-        || !ql_aligned(c0, 4) || !ql_aligned(cT, 4) || !ql_aligned(reserve, 4) || !ql_aligned(lengths, 4)) {
+    if (!aligned(zx, 16) || !aligned(h0, 16) || !aligned(y, 16) || !aligned(hT, 16) || !aligned(workspace, 16) || !aligned(R, 4)
+        || !aligned(c0, 4) || !aligned(cT, 4) || !aligned(reserve, 4) || !aligned(lengths, 4)) {
         set_error("%s: misaligned buffer (16 bytes for zx, h0, y, hT, workspace; 4 for the rest)", what);
         return QK_ERR_INVALID_ARG;
     }
     const size_t need = qk_qlstm_workspace_bytes(desc, QK_OP_FWD);
-    if (!workspace || workspace_bytes < need) { set_error("%s: workspace of %zu bytes needed, %zu given", what, need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    if (workspace_ok(what, workspace, workspace_bytes, need) != QK_OK) return QK_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const bool mfma = ql_path(desc) == QK_QLSTM_PATH_MFMA16;
     char *ws = (char *)workspace;
-    const size_t img = ql_image_bytes(desc, true), hb = ql_align(ql_state_elems(desc) * ql_esize(desc->dtype));
-    if (mfma) {
-        if (desc->dtype == QK_BF16) ql_launch_prep<bf16>(R, ws, desc, 1, st);
-        else ql_launch_prep<f16>(R, ws, desc, 1, st);
-    }
+    const size_t img = ql_image_bytes(desc, true), hb = align256(ql_state_elems(desc) * elem_size(desc->dtype));
+    if (mfma) by_dtype16(desc->dtype, [&](auto t) { ql_launch_prep<decltype(t)>(R, ws, desc, 1, st); });
     void *hbuf[2] = {ws + img, ws + img + hb};
     QlFwd a;
     a.B = desc->batch; a.T = desc->steps; a.Q = desc->q_units; a.D = desc->directions; a.ystride = desc->y_stride;
@@ -516,7 +479,7 @@ int qk_qlstm_fwd(const qk_qlstm_desc_t *desc, const void *zx, const float *R, co
         a.c_in = s == 0 ? c0 : cT;
         ql_launch_step<QlFwd>(desc, true, a, st);
     }
-    return ql_launched(what);
+    return launched(what);
 }
 
 int qk_qlstm_bwd(const qk_qlstm_desc_t *desc, const void *dy, const void *dhT, const float *dcT, const float *R, const int32_t *lengths,
@@ -526,22 +489,19 @@ int qk_qlstm_bwd(const qk_qlstm_desc_t *desc, const void *dy, const void *dhT, c
     const char *what = "qk_qlstm_bwd";
     if (!ql_desc_ok(desc, what)) return QK_ERR_INVALID_ARG;
     if (!dy || !R || !y || !reserve || !dzx || !hprev || !dh0 || !dc0) { set_error("%s: NULL buffer", what); return QK_ERR_INVALID_ARG; }
-    if (!ql_aligned(dy, 16) || !ql_aligned(dhT, 16) || !ql_aligned(h0, 16) || !ql_aligned(y, 16) || !ql_aligned(dzx, 16) || !ql_aligned(hprev, 16)
-        || !ql_aligned(dh0, 16) || !ql_aligned(workspace, 16) || !ql_aligned(R, 4) || !ql_aligned(dcT, 4) || !ql_aligned(c0, 4)
-        || !ql_aligned(reserve, 4) || !ql_aligned(dc0, 4) || !ql_aligned(lengths, 4)) {
+    if (!aligned(dy, 16) || !aligned(dhT, 16) || !aligned(h0, 16) || !aligned(y, 16) || !aligned(dzx, 16) || !aligned(hprev, 16)
+        || !aligned(dh0, 16) || !aligned(workspace, 16) || !aligned(R, 4) || !aligned(dcT, 4) || !aligned(c0, 4)
+        || !aligned(reserve, 4) || !aligned(dc0, 4) || !aligned(lengths, 4)) {
         set_error("%s: misaligned buffer (16 bytes for the activation buffers and the workspace; 4 for the rest)", what);
         return QK_ERR_INVALID_ARG;
     }
     const size_t need = qk_qlstm_workspace_bytes(desc, QK_OP_BWD);
-    if (!workspace || workspace_bytes < need) { set_error("%s: workspace of %zu bytes needed, %zu given", what, need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    if (workspace_ok(what, workspace, workspace_bytes, need) != QK_OK) return QK_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const bool mfma = ql_path(desc) == QK_QLSTM_PATH_MFMA16;
     char *ws = (char *)workspace;
     const size_t img = ql_image_bytes(desc, false);
-    if (mfma) {
-        if (desc->dtype == QK_BF16) ql_launch_prep<bf16>(R, ws, desc, 0, st);
-        else ql_launch_prep<f16>(R, ws, desc, 0, st);
-    }
+    if (mfma) by_dtype16(desc->dtype, [&](auto t) { ql_launch_prep<decltype(t)>(R, ws, desc, 0, st); });
     QlBwd a;
     a.B = desc->batch; a.T = desc->steps; a.Q = desc->q_units; a.D = desc->directions; a.ystride = desc->y_stride;
     a.rev0 = (desc->flags & QK_QLSTM_REVERSE) ? 1 : 0;
@@ -552,7 +512,7 @@ int qk_qlstm_bwd(const qk_qlstm_desc_t *desc, const void *dy, const void *dhT, c
         a.s = s;
         ql_launch_step<QlBwd>(desc, false, a, st);
     }
-    return ql_launched(what);
+    return launched(what);
 }
 
 }  // extern "C"

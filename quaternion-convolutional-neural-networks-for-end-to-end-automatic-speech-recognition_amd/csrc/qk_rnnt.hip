@@ -8,6 +8,7 @@
 // A (t, u) row is V elements -- 124 bytes at V = 62 in bf16 -- so a row is no unit for 16-byte accesses; 32 consecutive rows are
 // (32 V elements = 64 V or 128 V bytes), and that span is what a workgroup stages in LDS, as fp32, in both row kernels.
 #include "qk_common.h"
+#include "qk_seq.h"
 #include "../../include/qk_rnnt.h"
 
 #include <math.h>
@@ -240,8 +241,6 @@ bool rnnt_shape_ok(int B, int T, int U1, int V, const char *what)
     return true;
 }
 
-bool rnnt_dtype_ok(int dtype) { return dtype == QK_F32 || dtype == QK_BF16 || dtype == QK_F16; }
-
 size_t rnnt_ll_words(int B) { return (size_t)(B + 3) / 4 * 4; }
 
 template <typename T>
@@ -263,7 +262,7 @@ extern "C" {
 
 int qk_rnnt_supported(int32_t dtype, int32_t B, int32_t T, int32_t U1, int32_t V)
 {
-    if (!rnnt_dtype_ok(dtype)) { set_error("qk_rnnt_supported: unknown dtype %d", dtype); return 0; }
+    if (!dtype_known(dtype)) { set_error("qk_rnnt_supported: unknown dtype %d", dtype); return 0; }
     return rnnt_shape_ok(B, T, U1, V, "qk_rnnt_supported") ? 1 : 0;
 }
 
@@ -279,18 +278,17 @@ int qk_rnnt_loss(int32_t dtype, int32_t B, int32_t T, int32_t U1, int32_t V, con
                  size_t workspace_bytes, void *stream)
 {
     const char *what = "qk_rnnt_loss";
-    if (!rnnt_dtype_ok(dtype)) { set_error("%s: unknown dtype %d", what, dtype); return QK_ERR_INVALID_ARG; }
+    if (!dtype_known(dtype)) { set_error("%s: unknown dtype %d", what, dtype); return QK_ERR_INVALID_ARG; }
     if (!rnnt_shape_ok(B, T, U1, V, what)) return QK_ERR_UNSUPPORTED;
     if (!logits || !input_length || !label_length || !cost || (U1 > 1 && !labels)) { set_error("%s: NULL buffer", what); return QK_ERR_INVALID_ARG; }
-    const size_t es = dtype == QK_F32 ? 4 : 2;
-    const auto aligned = [](const void *q, size_t a) { return ((uintptr_t)q & (a - 1)) == 0; };
+    const size_t es = elem_size(dtype);
     if (!aligned(logits, es) || !aligned(grad, es) || !aligned(labels, 4) || !aligned(input_length, 4) || !aligned(label_length, 4)
         || !aligned(cost, 4) || !aligned(workspace, 16)) {
         set_error("%s: misaligned buffer (16 bytes for the workspace)", what);
         return QK_ERR_INVALID_ARG;
     }
     const size_t need = qk_rnnt_workspace_bytes(B, T, U1, V);
-    if (!workspace || workspace_bytes < need) { set_error("%s: workspace of %zu bytes needed, %zu given", what, need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    if (workspace_ok(what, workspace, workspace_bytes, need) != QK_OK) return QK_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const size_t R = (size_t)B * T * U1, Dg = (size_t)B * (T + U1 - 1) * U1;
     RnntArgs a = {};
@@ -302,24 +300,13 @@ int qk_rnnt_loss(int32_t dtype, int32_t B, int32_t T, int32_t U1, int32_t V, con
     // profiling only (QK_ABLATE / qk_set_debug_flags, as in the convolution launchers): 1 skips the row pass, 2 the lattice pass, 4 the
     // gradient pass.  A skipped pass leaves its outputs as the buffers held them; every pass only ever touches its own buffers.
     const int ablate = debug_ablate();
-    if (!(ablate & 1)) {
-        if (dtype == QK_F32) rnnt_launch_rows<float>(a, false, st);
-        else if (dtype == QK_BF16) rnnt_launch_rows<bf16>(a, false, st);
-        else rnnt_launch_rows<f16>(a, false, st);
-    }
+    if (!(ablate & 1)) by_dtype(dtype, [&](auto t) { rnnt_launch_rows<decltype(t)>(a, false, st); });
     if (!(ablate & 2)) {
         if (U1 <= 64) hipLaunchKernelGGL((k_rnnt_lattice<64>), dim3((unsigned)B, 2), dim3(64), 0, st, a);
         else hipLaunchKernelGGL((k_rnnt_lattice<128>), dim3((unsigned)B, 2), dim3(128), 0, st, a);
     }
-    if (grad && !(ablate & 4)) {
-        if (dtype == QK_F32) rnnt_launch_rows<float>(a, true, st);
-        else if (dtype == QK_BF16) rnnt_launch_rows<bf16>(a, true, st);
-        else rnnt_launch_rows<f16>(a, true, st);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return QK_OK;
-    set_error("%s: kernel launch failed: %s", what, hipGetErrorString(e));
-    return QK_ERR_LAUNCH;
+    if (grad && !(ablate & 4)) by_dtype(dtype, [&](auto t) { rnnt_launch_rows<decltype(t)>(a, true, st); });
+    return launched(what);
 }
 
 }  // extern "C"

@@ -2265,6 +2265,31 @@ def _aligned16(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+def _seq_path(symbol, desc, names):
+    """The name of the kernel family `symbol` (a qk_*_supported) reports for desc."""
+    path = getattr(L.lib(), symbol)(ctypes.byref(desc))
+    if path == 0:
+        L.check(L.QK_ERR_INVALID_ARG, symbol)
+    return names[path]
+
+
+def _lengths_arg(what, lengths, batch, device):
+    """lengths (or None) checked as an int32 (batch,) tensor on device, contiguous."""
+    if lengths is None:
+        return None
+    if lengths.dtype != torch.int32 or tuple(lengths.shape) != (batch,) or lengths.device != device:
+        raise ValueError('%s: lengths must be an int32 tensor of shape (%d,) on %s' % (what, batch, device))
+    return lengths.contiguous()
+
+
+def _bwd_workspace(symbol, desc, dev):
+    """(bytes, uint8 tensor): the backward workspace `symbol` (a qk_*_workspace_bytes) asks for.  Call inside _on_device(dev)."""
+    n = int(getattr(L.lib(), symbol)(ctypes.byref(desc), L.QK_OP_BWD))
+    if n == 0:
+        L.check(L.QK_ERR_INVALID_ARG, symbol)
+    return n, torch.empty(n, dtype=torch.uint8, device=dev)
+
+
 def qlstm_desc(dtype, batch, steps, q_units, directions, reverse=False):
     return L.QLSTMDesc(_DTYPES[dtype], int(batch), int(steps), int(q_units), int(directions), int(directions) * 4 * int(q_units),
                        L.QK_QLSTM_REVERSE if reverse else 0)
@@ -2272,11 +2297,7 @@ def qlstm_desc(dtype, batch, steps, q_units, directions, reverse=False):
 
 def qlstm_path(dtype, batch, steps, q_units, directions=1):
     """'mfma16' / 'generic': the kernel family qk_qlstm_fwd / qk_qlstm_bwd run for this shape (qk_qlstm_supported)."""
-    desc = qlstm_desc(dtype, batch, steps, q_units, directions)
-    path = L.lib().qk_qlstm_supported(ctypes.byref(desc))
-    if path == 0:
-        L.check(L.QK_ERR_INVALID_ARG, 'qk_qlstm_supported')
-    return L.QK_QLSTM_PATH_NAMES[path]
+    return _seq_path('qk_qlstm_supported', qlstm_desc(dtype, batch, steps, q_units, directions), L.QK_QLSTM_PATH_NAMES)
 
 
 class _QLSTMFn(torch.autograd.Function):
@@ -2318,11 +2339,9 @@ class _QLSTMFn(torch.autograd.Function):
         dh0 = torch.empty((D, B, U), dtype=dtype, device=dev)
         dc0 = torch.empty((D, B, U), dtype=torch.float32, device=dev)
         with _on_device(dev):
-            lib = L.lib()
-            n = int(lib.qk_qlstm_workspace_bytes(ctypes.byref(desc), L.QK_OP_BWD))
-            ws = torch.empty(n, dtype=torch.uint8, device=dev)
-            rc = lib.qk_qlstm_bwd(ctypes.byref(desc), _ptr(dy), _ptr(dhT), _ptr(dcT), _ptr(R), _ptr(lengths), _ptr(h0), _ptr(c0), _ptr(y),
-                                  _ptr(reserve), _ptr(dzx), _ptr(hprev), _ptr(dh0), _ptr(dc0), _ptr(ws), n, _stream(dy))
+            n, ws = _bwd_workspace('qk_qlstm_workspace_bytes', desc, dev)
+            rc = L.lib().qk_qlstm_bwd(ctypes.byref(desc), _ptr(dy), _ptr(dhT), _ptr(dcT), _ptr(R), _ptr(lengths), _ptr(h0), _ptr(c0), _ptr(y),
+                                      _ptr(reserve), _ptr(dzx), _ptr(hprev), _ptr(dh0), _ptr(dc0), _ptr(ws), n, _stream(dy))
         L.check(rc, 'qk_qlstm_bwd')
         dR = None
         if ctx.needs_input_grad[1]:
@@ -2363,10 +2382,7 @@ def qlstm(zx, R, lengths=None, h0=None, c0=None, reverse=False):
         raise ValueError('qlstm: reverse needs one direction')
     if B == 0 or T == 0:
         raise ValueError('qlstm: empty batch or sequence')
-    if lengths is not None:
-        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or lengths.device != zx.device:
-            raise ValueError('qlstm: lengths must be an int32 tensor of shape (%d,) on %s' % (B, zx.device))
-        lengths = lengths.contiguous()
+    lengths = _lengths_arg('qlstm', lengths, B, zx.device)
     for name, s, dt in (('h0', h0, zx.dtype), ('c0', c0, torch.float32)):
         if s is not None and (tuple(s.shape) != (D, B, U) or s.dtype != dt or s.device != zx.device):
             raise ValueError('qlstm: %s must be %s of shape %s on %s' % (name, dt, (D, B, U), zx.device))
@@ -2388,11 +2404,7 @@ def qlayer_norm_desc(dtype, rows, q, steps=0, x_stride=None, y_stride=None):
 def qlayer_norm_path(dtype, rows, q):
     """'vec' / 'generic': the kernel family qk_qlnorm_fwd / qk_qlnorm_bwd run for dense, 16-byte aligned rows of this shape
     (qk_qlnorm_supported)."""
-    desc = qlayer_norm_desc(dtype, rows, q)
-    path = L.lib().qk_qlnorm_supported(ctypes.byref(desc))
-    if path == 0:
-        L.check(L.QK_ERR_INVALID_ARG, 'qk_qlnorm_supported')
-    return L.QK_QLNORM_PATH_NAMES[path]
+    return _seq_path('qk_qlnorm_supported', qlayer_norm_desc(dtype, rows, q), L.QK_QLNORM_PATH_NAMES)
 
 
 def _rows_of(t, width):
@@ -2430,15 +2442,9 @@ class _QLNormFn(torch.autograd.Function):
         dgamma = torch.empty((W // 4,), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         dbeta = torch.empty((W,), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
         with _on_device(dev):
-            lib = L.lib()
-            n, ws = 0, None
-            if dgamma is not None or dbeta is not None:
-                n = int(lib.qk_qlnorm_workspace_bytes(ctypes.byref(desc), L.QK_OP_BWD))
-                if n == 0:
-                    L.check(L.QK_ERR_INVALID_ARG, 'qk_qlnorm_workspace_bytes')
-                ws = torch.empty(n, dtype=torch.uint8, device=dev)
-            rc = lib.qk_qlnorm_bwd(ctypes.byref(desc), _ptr(dy), _ptr(x), _ptr(gamma), _ptr(lengths), _ptr(stats), _ptr(dx), _ptr(dgamma),
-                                   _ptr(dbeta), _ptr(ws), n, _stream(x))
+            n, ws = (0, None) if dgamma is None and dbeta is None else _bwd_workspace('qk_qlnorm_workspace_bytes', desc, dev)
+            rc = L.lib().qk_qlnorm_bwd(ctypes.byref(desc), _ptr(dy), _ptr(x), _ptr(gamma), _ptr(lengths), _ptr(stats), _ptr(dx),
+                                       _ptr(dgamma), _ptr(dbeta), _ptr(ws), n, _stream(x))
         L.check(rc, 'qk_qlnorm_bwd')
         return dx, dgamma, dbeta, None, None, None
 
@@ -2459,9 +2465,7 @@ def qlayer_norm(x, gamma=None, beta=None, lengths=None, epsilon=1e-3):
     if lengths is not None:
         if x.dim() != 3:
             raise ValueError('qlayer_norm: lengths needs x of shape (B, T, 4 Q), got %s' % (tuple(x.shape),))
-        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (x.shape[0],) or lengths.device != x.device:
-            raise ValueError('qlayer_norm: lengths must be an int32 tensor of shape (%d,) on %s' % (x.shape[0], x.device))
-        lengths, steps = lengths.contiguous(), x.shape[1]
+        lengths, steps = _lengths_arg('qlayer_norm', lengths, x.shape[0], x.device), x.shape[1]
     for name, p, n in (('gamma', gamma, W // 4), ('beta', beta, W)):
         if p is not None and (p.dtype != torch.float32 or tuple(p.shape) != (n,) or p.device != x.device):
             raise ValueError('qlayer_norm: %s must be float32 of shape (%d,) on %s' % (name, n, x.device))
@@ -2484,11 +2488,7 @@ def qattention_path(dtype, batch, steps, heads, dq, packed=False):
     of this shape (qk_qattn_supported)."""
     Q = int(heads) * int(dq)
     s = (12 * Q, 3 * Q) if packed else None
-    desc = qattention_desc(dtype, batch, steps, heads, dq, s, s, s, None)
-    path = L.lib().qk_qattn_supported(ctypes.byref(desc))
-    if path == 0:
-        L.check(L.QK_ERR_INVALID_ARG, 'qk_qattn_supported')
-    return L.QK_QATTN_PATH_NAMES[path]
+    return _seq_path('qk_qattn_supported', qattention_desc(dtype, batch, steps, heads, dq, s, s, s, None), L.QK_QATTN_PATH_NAMES)
 
 
 def _attn_rows(t, width):
@@ -2516,13 +2516,9 @@ def _qattn_fwd(dtype, B, T, heads, dq, strides, ptrs, lengths, scale, dev, strea
 def _qattn_bwd(dtype, B, T, heads, dq, strides, ptrs, gptrs, do, o, lse, lengths, scale, dev):
     desc = qattention_desc(dtype, B, T, heads, dq, strides[0], strides[1], strides[2], None)
     with _on_device(dev):
-        lib = L.lib()
-        n = int(lib.qk_qattn_workspace_bytes(ctypes.byref(desc), L.QK_OP_BWD))
-        if n == 0:
-            L.check(L.QK_ERR_INVALID_ARG, 'qk_qattn_workspace_bytes')
-        ws = torch.empty(n, dtype=torch.uint8, device=dev)
-        rc = lib.qk_qattn_bwd(ctypes.byref(desc), _ptr(do), ptrs[0], ptrs[1], ptrs[2], _ptr(o), _ptr(lse), _ptr(lengths), float(scale),
-                              gptrs[0], gptrs[1], gptrs[2], _ptr(ws), n, _stream(do))
+        n, ws = _bwd_workspace('qk_qattn_workspace_bytes', desc, dev)
+        rc = L.lib().qk_qattn_bwd(ctypes.byref(desc), _ptr(do), ptrs[0], ptrs[1], ptrs[2], _ptr(o), _ptr(lse), _ptr(lengths),
+                                  float(scale), gptrs[0], gptrs[1], gptrs[2], _ptr(ws), n, _stream(do))
     L.check(rc, 'qk_qattn_bwd')
 
 
@@ -2582,10 +2578,7 @@ def _qattn_check(what, x, width_mult, heads, lengths, scale):
     if x.dim() != 3 or x.numel() == 0 or heads < 1 or x.shape[-1] % (width_mult * heads):
         raise ValueError('%s: needs a non-empty (B, T, %d Q) tensor with heads = %d dividing Q, got %s'
                          % (what, width_mult, heads, tuple(x.shape)))
-    if lengths is not None:
-        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (x.shape[0],) or lengths.device != x.device:
-            raise ValueError('%s: lengths must be an int32 tensor of shape (%d,) on %s' % (what, x.shape[0], x.device))
-        lengths = lengths.contiguous()
+    lengths = _lengths_arg(what, lengths, x.shape[0], x.device)
     if scale is None:
         scale = 0.0                                  # the library's default: 1 / sqrt(4 dq)
     elif not 0.0 < float(scale) < float('inf'):
@@ -2637,10 +2630,7 @@ def qdwconv_path(dtype, batch, steps, units, taps=15, packed=False):
     aligned tensors of this shape (qk_qdwconv_supported)."""
     Q = int(units)
     desc = qdwconv_desc(dtype, batch, steps, Q, taps, 0, (8 * Q, 2 * Q) if packed else None)
-    path = L.lib().qk_qdwconv_supported(ctypes.byref(desc))
-    if path == 0:
-        L.check(L.QK_ERR_INVALID_ARG, 'qk_qdwconv_supported')
-    return L.QK_QDWCONV_PATH_NAMES[path]
+    return _seq_path('qk_qdwconv_supported', desc, L.QK_QDWCONV_PATH_NAMES)
 
 
 def qdwconv_last_path():
@@ -2683,16 +2673,10 @@ class _QDWConvFn(torch.autograd.Function):
         dw = torch.empty(tuple(kernel.shape), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         dbias = torch.empty((4 * Q,), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
         with _on_device(dev):
-            lib = L.lib()
-            n, ws = 0, None
-            if dw is not None or dbias is not None:
-                n = int(lib.qk_qdwconv_workspace_bytes(ctypes.byref(desc), L.QK_OP_BWD))
-                if n == 0:
-                    L.check(L.QK_ERR_INVALID_ARG, 'qk_qdwconv_workspace_bytes')
-                ws = torch.empty(n, dtype=torch.uint8, device=dev)
-            rc = lib.qk_qdwconv_bwd(ctypes.byref(desc), dy.data_ptr(), x.data_ptr(), x.data_ptr() + Q * es if gated else None,
-                                    _ptr(kernel), _ptr(lengths), grad.data_ptr(), grad.data_ptr() + Q * es if gated else None,
-                                    _ptr(dw), _ptr(dbias), _ptr(ws), n, _stream(x))
+            n, ws = (0, None) if dw is None and dbias is None else _bwd_workspace('qk_qdwconv_workspace_bytes', desc, dev)
+            rc = L.lib().qk_qdwconv_bwd(ctypes.byref(desc), dy.data_ptr(), x.data_ptr(), x.data_ptr() + Q * es if gated else None,
+                                        _ptr(kernel), _ptr(lengths), grad.data_ptr(), grad.data_ptr() + Q * es if gated else None,
+                                        _ptr(dw), _ptr(dbias), _ptr(ws), n, _stream(x))
         L.check(rc, 'qk_qdwconv_bwd')
         return grad, dw, dbias, None, None, None
 
@@ -2708,10 +2692,7 @@ def _qdwconv(what, x, mult, kernel, bias, lengths, padding):
                          % (what, 4 * Q, x.device, kernel.dtype, tuple(kernel.shape)))
     if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (4 * Q,) or bias.device != x.device):
         raise ValueError('%s: bias must be float32 of shape (%d,) on %s' % (what, 4 * Q, x.device))
-    if lengths is not None:
-        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (x.shape[0],) or lengths.device != x.device:
-            raise ValueError('%s: lengths must be an int32 tensor of shape (%d,) on %s' % (what, x.shape[0], x.device))
-        lengths = lengths.contiguous()
+    lengths = _lengths_arg(what, lengths, x.shape[0], x.device)
     return _QDWConvFn.apply(x, kernel.contiguous(), bias.contiguous() if bias is not None else None, lengths,
                             qdwconv_pad_lo(kernel.shape[0], padding), mult == 8)
 
