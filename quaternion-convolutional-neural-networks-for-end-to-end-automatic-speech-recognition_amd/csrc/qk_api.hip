@@ -6,8 +6,9 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "qk_common.h"
+#include "qk_seq.h"
 
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <vector>
@@ -175,12 +176,8 @@ int launch_wgrad(int dtype, const void *x, const void *dy, const void *ymask, fl
 
 namespace {
 
-size_t elem_bytes(int dtype) { return dtype == QK_F32 ? 4 : 2; }
-
-bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 // 4-element vector loads need 16 B (f32) / 8 B (16-bit) alignment
-bool vec_aligned(const void *p, int dtype) { return aligned(p, 4 * elem_bytes(dtype)); }
+bool vec_aligned(const void *p, int dtype) { return aligned(p, 4 * elem_size(dtype)); }
 
 int validate(const qk_conv_desc_t *d, bool allow_rank0)
 {
@@ -296,7 +293,7 @@ size_t w_floats(const qk_conv_desc_t *d) { return (size_t)taps_of(d) * d->cq * 4
 size_t dy_bytes(const qk_conv_desc_t *d)
 {
     const size_t e = (size_t)d->batch * d->out_spatial[0] * d->out_spatial[1] * d->out_spatial[2] * 4 * d->fq;
-    return (e * elem_bytes(d->dtype) + 255) / 256 * 256;
+    return (e * elem_size(d->dtype) + 255) / 256 * 256;
 }
 
 // ---- channels_first 16-bit buffers on the matrix cores ----------------------------------------------------------
@@ -314,7 +311,6 @@ bool cf16_ok(const qk_conv_desc_t *d)
     for (int i = 0; i < 3; ++i) if (d->stride[i] != 1) return false;
     return true;
 }
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 size_t x_bytes16(const qk_conv_desc_t *d) { return align256((size_t)d->batch * d->in_spatial[0] * d->in_spatial[1] * d->in_spatial[2] * 4 * d->cq * 2); }
 size_t y_bytes16(const qk_conv_desc_t *d) { return align256((size_t)d->batch * d->out_spatial[0] * d->out_spatial[1] * d->out_spatial[2] * 4 * d->fq * 2); }
 int in_positions(const qk_conv_desc_t *d) { return d->in_spatial[0] * d->in_spatial[1] * d->in_spatial[2]; }
@@ -700,6 +696,50 @@ int check_launch(int rc, const char *what)
 {
     if (rc == QK_ERR_LAUNCH) set_error("%s: kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
     return rc;
+}
+
+// ---- the CTC family: the checks that are the same words in several entry points; `what` is the name inside the message
+template <typename... A>
+int fail(int rc, const char *fmt, A... a) { set_error(fmt, a...); return rc; }          // the message, then the code
+int null_arg(const char *what) { return fail(QK_ERR_INVALID_ARG, "%s: NULL argument", what); }
+int lattice_extents_ok(const char *what, int batch, int frames, int classes, int max_label_len)
+{
+    if (batch > 0 && frames > 0 && classes >= 2 && max_label_len >= 0) return QK_OK;
+    return fail(QK_ERR_INVALID_ARG, "%s: bad extents (%d, %d, %d, %d)", what, batch, frames, classes, max_label_len);
+}
+int count_ok(const char *what, long long elements)          // the kernels index with int
+{
+    return elements <= INT_MAX ? QK_OK : fail(QK_ERR_UNSUPPORTED, "%s: tensor with >= 2^31 elements", what);
+}
+int ctc_workspace_ok(const char *what, const void *workspace, size_t given, size_t need, size_t alignment)
+{
+    if (workspace && given >= need && aligned(workspace, alignment)) return QK_OK;
+    return fail(QK_ERR_WORKSPACE, alignment == 8 ? "%s needs %zu workspace bytes (8-byte aligned), got %zu" : "%s needs %zu workspace bytes, got %zu",
+                what, need, given);
+}
+
+// what qk_ctc_beam_search_decode_lm checks on top of qk_ctc_beam_search_decode, each at its place in the common order
+struct BeamLmArgs { int order; const float *table; float weight, bonus; const float *score; };
+int beam_args_ok(const char *what, int dtype, int batch, int frames, int classes, const void *y_pred, const int32_t *input_length,
+                        int beam_width, int top_paths, const int32_t *decoded, const int32_t *decoded_len, const float *log_prob,
+                        const void *workspace, size_t workspace_bytes, const BeamLmArgs *lm)
+{
+    if (batch <= 0 || frames <= 0 || classes < 2 || beam_width < 1 || top_paths < 1 || dtype < QK_F32 || dtype > QK_F16)
+        return fail(QK_ERR_INVALID_ARG, "%s: bad arguments (%d, %d, %d, beam %d, paths %d, dtype %d)", what, batch, frames, classes, beam_width,
+                    top_paths, dtype);
+    if (lm && (!(lm->weight >= 0.f) || !isfinite(lm->weight) || !isfinite(lm->bonus)))
+        return fail(QK_ERR_INVALID_ARG, "%s: lm_weight %g must be finite and >= 0, insertion_bonus %g finite", what, (double)lm->weight,
+                    (double)lm->bonus);
+    if (lm && (lm->order < 1 || lm->order > 3)) return fail(QK_ERR_UNSUPPORTED, "%s: lm_order %d outside 1 .. 3", what, lm->order);
+    if (!y_pred || !input_length || !decoded || !decoded_len || !log_prob || (lm && (!lm->score || !lm->table))) return null_arg(what);
+    if (classes > 256 || beam_width > 128 || top_paths > beam_width)
+        return fail(QK_ERR_UNSUPPORTED, "%s: unsupported (classes %d <= 256, beam_width %d <= 128, top_paths %d <= beam_width)", what, classes,
+                    beam_width, top_paths);
+    if (lm && lm->order == 3 && classes > 64) return fail(QK_ERR_UNSUPPORTED, "%s: a trigram LM needs classes %d <= 64", what, classes);
+    if (lm && !ctc_beam_lm_supported(classes, beam_width, lm->order))
+        return fail(QK_ERR_UNSUPPORTED, "%s: the LM rows of %d beams x %d classes exceed the LDS budget", what, beam_width, classes);
+    if (const int rc = count_ok(what, std::max((long long)batch * frames * classes, (long long)top_paths * batch * frames))) return rc;
+    return ctc_workspace_ok(what, workspace, workspace_bytes, ctc_beam_workspace_bytes(batch, frames, beam_width), 4);
 }
 
 }  // namespace
@@ -1127,19 +1167,17 @@ int qk_maxpool2d_bwd(const qk_pool_desc_t *desc, const void *x, const void *dy, 
 
 size_t qk_ctc_workspace_bytes(int32_t batch, int32_t frames, int32_t max_label_len)
 {
-    if (batch <= 0 || frames <= 0 || max_label_len < 0) return 0;
-    return ctc_workspace_bytes(batch, frames, max_label_len);
+    return (batch <= 0 || frames <= 0 || max_label_len < 0) ? 0 : ctc_workspace_bytes(batch, frames, max_label_len);
 }
 
 int qk_ctc_batch_cost(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *labels,
                       int32_t max_label_len, const int32_t *input_length, const int32_t *label_length, float *cost, void *dy_pred,
                       void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (batch <= 0 || frames <= 0 || classes < 2 || max_label_len < 0) { set_error("ctc: bad extents (%d, %d, %d, %d)", batch, frames, classes, max_label_len); return QK_ERR_INVALID_ARG; }
-    if (!y_pred || !input_length || !label_length || !cost || (max_label_len > 0 && !labels)) { set_error("ctc: NULL argument"); return QK_ERR_INVALID_ARG; }
-    const size_t need = ctc_workspace_bytes(batch, frames, max_label_len);
-    if (!workspace || workspace_bytes < need || !aligned(workspace, 4)) { set_error("ctc needs %zu workspace bytes, got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE; }
-    if ((long long)batch * frames * classes > INT_MAX) { set_error("ctc: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
+    if (int rc = lattice_extents_ok("ctc", batch, frames, classes, max_label_len)) return rc;
+    if (!y_pred || !input_length || !label_length || !cost || (max_label_len > 0 && !labels)) return null_arg("ctc");
+    if (int rc = ctc_workspace_ok("ctc", workspace, workspace_bytes, ctc_workspace_bytes(batch, frames, max_label_len), 4)) return rc;
+    if (int rc = count_ok("ctc", (long long)batch * frames * classes)) return rc;
     const int rc = launch_ctc(dtype, batch, frames, classes, y_pred, labels, max_label_len, input_length, label_length, cost, dy_pred,
                               static_cast<float *>(workspace), (hipStream_t)stream);
     if (rc == QK_ERR_UNSUPPORTED) set_error("ctc: more than 127 labels, more than 256 classes or too many frames for one workgroup's LDS");
@@ -1149,36 +1187,27 @@ int qk_ctc_batch_cost(int32_t dtype, int32_t batch, int32_t frames, int32_t clas
 int qk_ctc_greedy_decode(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *input_length,
                          int32_t *decoded, int32_t *decoded_len, float *log_prob, void *stream)
 {
-    if (batch <= 0 || frames <= 0 || classes < 2 || dtype < QK_F32 || dtype > QK_F16) { set_error("ctc_greedy_decode: bad arguments (%d, %d, %d, dtype %d)", batch, frames, classes, dtype); return QK_ERR_INVALID_ARG; }
-    if (!y_pred || !input_length || !decoded || !decoded_len || !log_prob) { set_error("ctc_greedy_decode: NULL argument"); return QK_ERR_INVALID_ARG; }
-    if (classes > 256) { set_error("ctc_greedy_decode: more than 256 classes"); return QK_ERR_UNSUPPORTED; }
-    if ((long long)batch * frames * classes > INT_MAX) { set_error("ctc_greedy_decode: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
+    if (batch <= 0 || frames <= 0 || classes < 2 || dtype < QK_F32 || dtype > QK_F16)
+        return fail(QK_ERR_INVALID_ARG, "ctc_greedy_decode: bad arguments (%d, %d, %d, dtype %d)", batch, frames, classes, dtype);
+    if (!y_pred || !input_length || !decoded || !decoded_len || !log_prob) return null_arg("ctc_greedy_decode");
+    if (classes > 256) return fail(QK_ERR_UNSUPPORTED, "ctc_greedy_decode: more than 256 classes");
+    if (int rc = count_ok("ctc_greedy_decode", (long long)batch * frames * classes)) return rc;
     return check_launch(launch_ctc_greedy(dtype, batch, frames, classes, y_pred, input_length, decoded, decoded_len, log_prob,
                                           (hipStream_t)stream), "qk_ctc_greedy_decode");
 }
 
 size_t qk_ctc_beam_workspace_bytes(int32_t batch, int32_t frames, int32_t beam_width)
 {
-    if (batch <= 0 || frames <= 0 || beam_width <= 0) return 0;
-    return ctc_beam_workspace_bytes(batch, frames, beam_width);
+    return (batch <= 0 || frames <= 0 || beam_width <= 0) ? 0 : ctc_beam_workspace_bytes(batch, frames, beam_width);
 }
 
 int qk_ctc_beam_search_decode(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *input_length,
                               int32_t beam_width, int32_t top_paths, int32_t merge_repeated, int32_t *decoded, int32_t *decoded_len,
                               float *log_prob, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (batch <= 0 || frames <= 0 || classes < 2 || beam_width < 1 || top_paths < 1 || dtype < QK_F32 || dtype > QK_F16) {
-        set_error("ctc_beam_search_decode: bad arguments (%d, %d, %d, beam %d, paths %d, dtype %d)", batch, frames, classes, beam_width, top_paths, dtype);
-        return QK_ERR_INVALID_ARG;
-    }
-    if (!y_pred || !input_length || !decoded || !decoded_len || !log_prob) { set_error("ctc_beam_search_decode: NULL argument"); return QK_ERR_INVALID_ARG; }
-    if (classes > 256 || beam_width > 128 || top_paths > beam_width) {
-        set_error("ctc_beam_search_decode: unsupported (classes %d <= 256, beam_width %d <= 128, top_paths %d <= beam_width)", classes, beam_width, top_paths);
-        return QK_ERR_UNSUPPORTED;
-    }
-    if ((long long)batch * frames * classes > INT_MAX || (long long)top_paths * batch * frames > INT_MAX) { set_error("ctc_beam_search_decode: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
-    const size_t need = ctc_beam_workspace_bytes(batch, frames, beam_width);
-    if (!workspace || workspace_bytes < need || !aligned(workspace, 4)) { set_error("ctc_beam_search_decode needs %zu workspace bytes, got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    if (int rc = beam_args_ok("ctc_beam_search_decode", dtype, batch, frames, classes, y_pred, input_length, beam_width, top_paths, decoded,
+                              decoded_len, log_prob, workspace, workspace_bytes, nullptr))
+        return rc;
     return check_launch(launch_ctc_beam(dtype, batch, frames, classes, y_pred, input_length, beam_width, top_paths, merge_repeated,
                                         decoded, decoded_len, log_prob, static_cast<int *>(workspace), (hipStream_t)stream),
                         "qk_ctc_beam_search_decode");
@@ -1190,28 +1219,10 @@ int qk_ctc_beam_search_decode_lm(int32_t dtype, int32_t batch, int32_t frames, i
                                  int32_t *decoded, int32_t *decoded_len, float *log_prob, float *score,
                                  void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (batch <= 0 || frames <= 0 || classes < 2 || beam_width < 1 || top_paths < 1 || dtype < QK_F32 || dtype > QK_F16) {
-        set_error("ctc_beam_search_decode_lm: bad arguments (%d, %d, %d, beam %d, paths %d, dtype %d)", batch, frames, classes, beam_width, top_paths, dtype);
-        return QK_ERR_INVALID_ARG;
-    }
-    if (!(lm_weight >= 0.f) || !isfinite(lm_weight) || !isfinite(insertion_bonus)) {
-        set_error("ctc_beam_search_decode_lm: lm_weight %g must be finite and >= 0, insertion_bonus %g finite", (double)lm_weight, (double)insertion_bonus);
-        return QK_ERR_INVALID_ARG;
-    }
-    if (lm_order < 1 || lm_order > 3) { set_error("ctc_beam_search_decode_lm: lm_order %d outside 1 .. 3", lm_order); return QK_ERR_UNSUPPORTED; }
-    if (!y_pred || !input_length || !decoded || !decoded_len || !log_prob || !score || !lm_table) { set_error("ctc_beam_search_decode_lm: NULL argument"); return QK_ERR_INVALID_ARG; }
-    if (classes > 256 || beam_width > 128 || top_paths > beam_width) {
-        set_error("ctc_beam_search_decode_lm: unsupported (classes %d <= 256, beam_width %d <= 128, top_paths %d <= beam_width)", classes, beam_width, top_paths);
-        return QK_ERR_UNSUPPORTED;
-    }
-    if (lm_order == 3 && classes > 64) { set_error("ctc_beam_search_decode_lm: a trigram LM needs classes %d <= 64", classes); return QK_ERR_UNSUPPORTED; }
-    if (!ctc_beam_lm_supported(classes, beam_width, lm_order)) {
-        set_error("ctc_beam_search_decode_lm: the LM rows of %d beams x %d classes exceed the LDS budget", beam_width, classes);
-        return QK_ERR_UNSUPPORTED;
-    }
-    if ((long long)batch * frames * classes > INT_MAX || (long long)top_paths * batch * frames > INT_MAX) { set_error("ctc_beam_search_decode_lm: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
-    const size_t need = ctc_beam_workspace_bytes(batch, frames, beam_width);
-    if (!workspace || workspace_bytes < need || !aligned(workspace, 4)) { set_error("ctc_beam_search_decode_lm needs %zu workspace bytes, got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE; }
+    const BeamLmArgs lm = {lm_order, lm_table, lm_weight, insertion_bonus, score};
+    if (int rc = beam_args_ok("ctc_beam_search_decode_lm", dtype, batch, frames, classes, y_pred, input_length, beam_width, top_paths,
+                              decoded, decoded_len, log_prob, workspace, workspace_bytes, &lm))
+        return rc;
     return check_launch(launch_ctc_beam_lm(dtype, batch, frames, classes, y_pred, input_length, beam_width, top_paths, merge_repeated, lm_order,
                                            lm_table, lm_weight, insertion_bonus, lm_eos, decoded, decoded_len, log_prob, score,
                                            static_cast<int *>(workspace), (hipStream_t)stream),
@@ -1221,9 +1232,10 @@ int qk_ctc_beam_search_decode_lm(int32_t dtype, int32_t batch, int32_t frames, i
 int qk_edit_distance(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const int32_t *hyp_len, const int32_t *ref, int32_t ref_stride,
                      const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *distance, int32_t *ref_len_out, void *stream)
 {
-    if (batch <= 0 || hyp_stride < 0 || ref_stride < 0 || (class_map && classes <= 0)) { set_error("edit_distance: bad arguments (%d, %d, %d, %d)", batch, hyp_stride, ref_stride, classes); return QK_ERR_INVALID_ARG; }
-    if (!hyp_len || !ref_len || !distance || (hyp_stride > 0 && !hyp) || (ref_stride > 0 && !ref)) { set_error("edit_distance: NULL argument"); return QK_ERR_INVALID_ARG; }
-    if (ref_stride > 1024) { set_error("edit_distance: reference longer than 1024 tokens (stride %d)", ref_stride); return QK_ERR_UNSUPPORTED; }
+    if (batch <= 0 || hyp_stride < 0 || ref_stride < 0 || (class_map && classes <= 0))
+        return fail(QK_ERR_INVALID_ARG, "edit_distance: bad arguments (%d, %d, %d, %d)", batch, hyp_stride, ref_stride, classes);
+    if (!hyp_len || !ref_len || !distance || (hyp_stride > 0 && !hyp) || (ref_stride > 0 && !ref)) return null_arg("edit_distance");
+    if (ref_stride > 1024) return fail(QK_ERR_UNSUPPORTED, "edit_distance: reference longer than 1024 tokens (stride %d)", ref_stride);
     return check_launch(launch_edit_distance(batch, hyp, hyp_stride, hyp_len, ref, ref_stride, ref_len, class_map, class_map ? classes : 0,
                                              distance, ref_len_out, (hipStream_t)stream), "qk_edit_distance");
 }
@@ -1238,25 +1250,17 @@ int qk_edit_align(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const i
                   const int32_t *ref_len, const int32_t *class_map, int32_t classes, int32_t *counts, int32_t *ali_ref, int32_t *ali_hyp,
                   int32_t *ali_len, int32_t *confusion, int32_t out_classes, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (batch < 0 || hyp_stride < 0 || ref_stride < 0 || (class_map && classes <= 0) || (confusion && out_classes < 0)) {
-        set_error("edit_align: bad arguments (%d, %d, %d, %d, %d)", batch, hyp_stride, ref_stride, classes, out_classes); return QK_ERR_INVALID_ARG;
-    }
-    if (hyp_stride > 1024 || ref_stride > 1024 || (confusion && out_classes > 256)) {
-        set_error("edit_align: unsupported (hyp_stride %d <= 1024, ref_stride %d <= 1024, out_classes %d <= 256)", hyp_stride, ref_stride,
-                  confusion ? out_classes : 0);
-        return QK_ERR_UNSUPPORTED;
-    }
+    if (batch < 0 || hyp_stride < 0 || ref_stride < 0 || (class_map && classes <= 0) || (confusion && out_classes < 0))
+        return fail(QK_ERR_INVALID_ARG, "edit_align: bad arguments (%d, %d, %d, %d, %d)", batch, hyp_stride, ref_stride, classes, out_classes);
+    if (hyp_stride > 1024 || ref_stride > 1024 || (confusion && out_classes > 256))
+        return fail(QK_ERR_UNSUPPORTED, "edit_align: unsupported (hyp_stride %d <= 1024, ref_stride %d <= 1024, out_classes %d <= 256)", hyp_stride,
+                    ref_stride, confusion ? out_classes : 0);
     if (batch == 0) return 0;
-    if (!hyp_len || !ref_len || !counts || (hyp_stride > 0 && !hyp) || (ref_stride > 0 && !ref)) {
-        set_error("edit_align: NULL argument"); return QK_ERR_INVALID_ARG;
-    }
-    if ((ali_ref != nullptr) != (ali_hyp != nullptr) || (ali_ref != nullptr) != (ali_len != nullptr)) {
-        set_error("edit_align: ali_ref, ali_hyp and ali_len are NULL together or not at all"); return QK_ERR_INVALID_ARG;
-    }
+    if (!hyp_len || !ref_len || !counts || (hyp_stride > 0 && !hyp) || (ref_stride > 0 && !ref)) return null_arg("edit_align");
+    if ((ali_ref != nullptr) != (ali_hyp != nullptr) || (ali_ref != nullptr) != (ali_len != nullptr))
+        return fail(QK_ERR_INVALID_ARG, "edit_align: ali_ref, ali_hyp and ali_len are NULL together or not at all");
     const size_t need = edit_align_workspace_bytes(batch, hyp_stride, ref_stride);
-    if (need > 0 && (!workspace || workspace_bytes < need || !aligned(workspace, 8))) {
-        set_error("edit_align needs %zu workspace bytes (8-byte aligned), got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE;
-    }
+    if (int rc = need > 0 ? ctc_workspace_ok("edit_align", workspace, workspace_bytes, need, 8) : QK_OK) return rc;
     return check_launch(launch_edit_align(batch, hyp, hyp_stride, hyp_len, ref, ref_stride, ref_len, class_map, class_map ? classes : 0,
                                           counts, ali_ref, ali_hyp, ali_len, confusion, confusion ? out_classes : 0, workspace,
                                           (hipStream_t)stream), "qk_edit_align");
@@ -1264,33 +1268,24 @@ int qk_edit_align(int32_t batch, const int32_t *hyp, int32_t hyp_stride, const i
 
 size_t qk_ctc_align_workspace_bytes(int32_t batch, int32_t frames, int32_t max_label_len)
 {
-    if (batch <= 0 || frames <= 0 || max_label_len < 0) return 0;
-    return ctc_align_workspace_bytes(batch, frames);
+    return (batch <= 0 || frames <= 0 || max_label_len < 0) ? 0 : ctc_align_workspace_bytes(batch, frames);
 }
 
 int qk_ctc_forced_align(int32_t dtype, int32_t batch, int32_t frames, int32_t classes, const void *y_pred, const int32_t *labels,
                         int32_t max_label_len, const int32_t *input_length, const int32_t *label_length, int32_t *path,
                         int32_t *starts, int32_t *ends, float *score, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (batch <= 0 || frames <= 0 || classes < 2 || max_label_len < 0) {
-        set_error("ctc_forced_align: bad extents (%d, %d, %d, %d)", batch, frames, classes, max_label_len); return QK_ERR_INVALID_ARG;
-    }
-    if (classes > 256 || max_label_len > 127 || dtype < QK_F32 || dtype > QK_F16) {
-        set_error("ctc_forced_align: unsupported (classes %d <= 256, max_label_len %d <= 127, dtype %d one of fp32 / bf16 / fp16)", classes,
-                  max_label_len, dtype);
-        return QK_ERR_UNSUPPORTED;
-    }
-    if (!y_pred || !input_length || !label_length || !path || !score || (max_label_len > 0 && (!labels || !starts || !ends))) {
-        set_error("ctc_forced_align: NULL argument"); return QK_ERR_INVALID_ARG;
-    }
-    if ((long long)batch * frames * classes > INT_MAX) { set_error("ctc_forced_align: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
-    if (!ctc_align_supported(frames, classes, max_label_len)) {
-        set_error("ctc_forced_align: %d frames are too many for one workgroup's LDS", frames); return QK_ERR_UNSUPPORTED;
-    }
-    const size_t need = ctc_align_workspace_bytes(batch, frames);
-    if (!workspace || workspace_bytes < need || !aligned(workspace, 8)) {
-        set_error("ctc_forced_align needs %zu workspace bytes (8-byte aligned), got %zu", need, workspace_bytes); return QK_ERR_WORKSPACE;
-    }
+    const char *what = "ctc_forced_align";
+    if (int rc = lattice_extents_ok(what, batch, frames, classes, max_label_len)) return rc;
+    if (classes > 256 || max_label_len > 127 || dtype < QK_F32 || dtype > QK_F16)
+        return fail(QK_ERR_UNSUPPORTED, "%s: unsupported (classes %d <= 256, max_label_len %d <= 127, dtype %d one of fp32 / bf16 / fp16)", what,
+                    classes, max_label_len, dtype);
+    if (!y_pred || !input_length || !label_length || !path || !score || (max_label_len > 0 && (!labels || !starts || !ends)))
+        return null_arg(what);
+    if (int rc = count_ok(what, (long long)batch * frames * classes)) return rc;
+    if (!ctc_align_supported(frames, classes, max_label_len))
+        return fail(QK_ERR_UNSUPPORTED, "%s: %d frames are too many for one workgroup's LDS", what, frames);
+    if (int rc = ctc_workspace_ok(what, workspace, workspace_bytes, ctc_align_workspace_bytes(batch, frames), 8)) return rc;
     return check_launch(launch_ctc_align(dtype, batch, frames, classes, y_pred, labels, max_label_len, input_length, label_length, path,
                                          starts, ends, score, workspace, (hipStream_t)stream), "qk_ctc_forced_align");
 }
@@ -1378,8 +1373,8 @@ int qk_spec_augment(int32_t in_dtype, int32_t out_dtype, int32_t batch, int32_t 
     }
     const long long count = (long long)batch * planes * rows * frames;
     if (count > INT_MAX) { set_error("spec_augment: tensor with >= 2^31 elements"); return QK_ERR_UNSUPPORTED; }
-    const size_t in_bytes = (size_t)count * elem_bytes(in_dtype), out_bytes = (size_t)count * elem_bytes(out_dtype);
-    if (!aligned(x, elem_bytes(in_dtype)) || !aligned(out, elem_bytes(out_dtype)) || (plan && !aligned(plan, 4))) {
+    const size_t in_bytes = (size_t)count * elem_size(in_dtype), out_bytes = (size_t)count * elem_size(out_dtype);
+    if (!aligned(x, elem_size(in_dtype)) || !aligned(out, elem_size(out_dtype)) || (plan && !aligned(plan, 4))) {
         set_error("spec_augment: x, out and plan must be aligned to their element size"); return QK_ERR_INVALID_ARG;
     }
     const uintptr_t xa = reinterpret_cast<uintptr_t>(x), oa = reinterpret_cast<uintptr_t>(out);

@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "../../include/qk.h"
 
 namespace qk {
@@ -446,5 +448,25 @@ inline int debug_ablate() { return (int)((debug_flags() & kDbgAblateMask) >> kDb
 bool debug_force_cfg(int *policy, int *bq);
 // compute units x resident workgroups of a kernel, queried per call from the current device (no caching)
 int device_cu_count();
+
+// More than 64 KB of dynamic LDS must be asked for explicitly, per kernel.  The attribute belongs to the DEVICE's copy of the function,
+// so each kernel instantiation keeps the largest size granted so far per device (`granted`: a function-local static of its launcher)
+// and the attribute call is made only when a launch needs more.  false: the device refused; HIP's error is left in place for a caller
+// that reports it, and a caller for which a refusal is no error (it takes a smaller form) clears it.
+constexpr int kMaxLdsDevices = 64;
+inline int lds_device()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxLdsDevices) { (void)hipGetLastError(); dev = 0; }
+    return dev;
+}
+inline bool grant_dynamic_lds(const void *kernel, size_t bytes, std::atomic<int> (&granted)[kMaxLdsDevices])
+{
+    const int dev = lds_device();
+    if ((int)bytes <= granted[dev].load(std::memory_order_relaxed)) return true;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
+    granted[dev].store((int)bytes, std::memory_order_relaxed);
+    return true;
+}
 
 }  // namespace qk

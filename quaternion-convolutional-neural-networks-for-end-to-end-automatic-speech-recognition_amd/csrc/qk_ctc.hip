@@ -13,29 +13,15 @@
 // extended label sequence (blank, l1, blank, l2, ..., blank: S = 2 L + 1 states), alpha / beta of the previous frame sit in
 // LDS (one barrier per frame), alpha of every frame goes to a workspace for the backward sweep, the emission of the NEXT
 // frame is fetched before the barrier of the current one.  Latency-bound by construction (T dependent steps): ~0.1 ms.
-#include "qk_common.h"
-#include <atomic>
+#include "qk_ctc_lattice.h"
+#include "qk_seq.h"
 
 namespace qk {
 namespace {
 
-constexpr float kNegInf = -1e30f;
 constexpr int CTC_THREADS = 256;
 
-__device__ __forceinline__ float lse2(float a, float b)
-{
-    const float m = fmaxf(a, b);
-    if (m <= -1e29f) return kNegInf;
-    return m + __logf(__expf(a - m) + __expf(b - m));
-}
-__device__ __forceinline__ float lse3(float a, float b, float c)
-{
-    const float m = fmaxf(a, fmaxf(b, c));
-    if (m <= -1e29f) return kNegInf;
-    return m + __logf(__expf(a - m) + __expf(b - m) + __expf(c - m));
-}
-
-struct CtcGeom { int B, T, C, Lmax, Smax; float eps; int det; };      // det (QK_DBG_DETERMINISTIC): occupancies summed in a fixed order
+struct CtcGeom : LatticeGeom { int det; };      // det (QK_DBG_DETERMINISTIC): occupancies summed in a fixed order
 
 // LPS: the whole (T, C) log-probability table of the sample fits in LDS (TIMIT: 200 x 62 floats = 50 KB) and is built once, with
 // coalesced loads -- every emission of the two sweeps and the gradient then comes from LDS; otherwise emissions are gathered from
@@ -85,7 +71,7 @@ k_ctc(const T *__restrict__ pred, const int *__restrict__ labels, const int *__r
     for (int i = tid; i < 2 * g.C; i += CTC_THREADS) acc2[i] = 0.f;      // C may reach CTC_THREADS: both parity tables
     __syncthreads();
     if constexpr (LPS) {
-        for (int e = tid; e < Tn * g.C; e += CTC_THREADS) lpt[e] -= lse[e / g.C];
+        lattice_normalise<CTC_THREADS>(lpt, lse, Tn * g.C, g.C, tid);
         __syncthreads();
     }
     auto emit = [&](int t) -> float {          // lp[t][class of this state]
@@ -114,7 +100,7 @@ k_ctc(const T *__restrict__ pred, const int *__restrict__ labels, const int *__r
         if (live && t + 1 < Tn) e_next = emit(t + 1);              // in flight across the barrier
         if (live) {
             const float a = lse3(ap[s], s >= 1 ? ap[s - 1] : kNegInf, skip_ok ? ap[s - 2] : kNegInf);
-            const float v = a <= -1e29f ? kNegInf : a + e_cur;
+            const float v = a <= kDead ? kNegInf : a + e_cur;
             an[s] = v;
             aws[(long long)t * g.Smax + s] = v;
         }
@@ -124,12 +110,12 @@ k_ctc(const T *__restrict__ pred, const int *__restrict__ labels, const int *__r
         const float *al = ab0 + ((Tn - 1) & 1) * g.Smax;
         const float ll = lse2(al[S - 1], S >= 2 ? al[S - 2] : kNegInf);
         nll_s[0] = -ll;
-        cost[b] = ll <= -1e29f ? INFINITY : -ll;
+        cost[b] = ll <= kDead ? INFINITY : -ll;
     }
     __syncthreads();
     if (!dpred) return;
     const float nll = nll_s[0];
-    if (nll >= 1e29f) {
+    if (nll >= -kDead) {
         // no alignment fits (more labels, counting the blanks between repeats, than frames): the cost is +inf and has no
         // gradient.  (TensorFlow's ctc_loss raises "Not enough time for target transition sequence" here; a finite
         // softmax / (p + eps) "gradient" with all occupancies zero would push the optimiser somewhere meaningless.)
@@ -151,13 +137,13 @@ k_ctc(const T *__restrict__ pred, const int *__restrict__ labels, const int *__r
             if (t == Tn - 1) bt = (s == S - 1 || s == S - 2) ? e_cur : kNegInf;
             else {
                 const float v = lse3(bp[s], s + 1 < S ? bp[s + 1] : kNegInf, skip_fw ? bp[s + 2] : kNegInf);
-                bt = v <= -1e29f ? kNegInf : v + e_cur;
+                bt = v <= kDead ? kNegInf : v + e_cur;
             }
             bn[s] = bt;
         }
         // occupancy of this state at frame t: alpha and beta both hold the emission of frame t
         float q = 0.f;
-        if (live && a_cur > -1e29f && bt > -1e29f) q = __expf(a_cur + bt - e_cur + nll);
+        if (live && a_cur > kDead && bt > kDead) q = __expf(a_cur + bt - e_cur + nll);
         // blanks (even states) are half of the states: reduce them inside the wave first, one LDS atomic per wave
         float *acc = acc2 + (t & 1) * g.C, *qs = qs2 + (t & 1) * g.Smax;
         if (g.det) {
@@ -249,7 +235,7 @@ k_ctc_fast(const T *__restrict__ pred, const int *__restrict__ labels, const int
         lse[t] = m + __logf(sum);
     }
     __syncthreads();
-    for (int e = tid; e < Tn * g.C; e += CTCF_THREADS) lpt[e] -= lse[e / g.C];
+    lattice_normalise<CTCF_THREADS>(lpt, lse, Tn * g.C, g.C, tid);
     if (Tn == 0) {             // no frames: the empty labelling has probability 1, any other is impossible
         if (tid == 0) cost[b] = S > 1 ? INFINITY : 0.f;
         if (dpred) for (int e = tid; e < g.T * g.C; e += CTCF_THREADS) dpred[(long long)b * g.T * g.C + e] = from_f32<T>(0.f);
@@ -271,10 +257,10 @@ k_ctc_fast(const T *__restrict__ pred, const int *__restrict__ labels, const int
                 v = start ? e : kNegInf;
             } else if (beta_half) {
                 const float a = lse3(prev[s], s + 1 < S ? prev[s + 1] : kNegInf, skip_fw ? prev[s + 2] : kNegInf);
-                v = a <= -1e29f ? kNegInf : a + e;
+                v = a <= kDead ? kNegInf : a + e;
             } else {
                 const float a = lse3(prev[s], s >= 1 ? prev[s - 1] : kNegInf, skip_bw ? prev[s - 2] : kNegInf);
-                v = a <= -1e29f ? kNegInf : a + e;
+                v = a <= kDead ? kNegInf : a + e;
             }
             buf[(i & 1) * g.Smax + s] = v;
             lat[(long long)t * g.Smax + s] = v;
@@ -285,14 +271,14 @@ k_ctc_fast(const T *__restrict__ pred, const int *__restrict__ labels, const int
         const float *al = aa + ((Tn - 1) & 1) * g.Smax;
         const float ll = lse2(al[S - 1], S >= 2 ? al[S - 2] : kNegInf);
         nll_s[0] = -ll;
-        cost[b] = ll <= -1e29f ? INFINITY : -ll;
+        cost[b] = ll <= kDead ? INFINITY : -ll;
     }
     __syncthreads();
     if (!dpred) return;
     const float nll = nll_s[0];
     T *dp = dpred + (long long)b * g.T * g.C;
     for (int e = Tn * g.C + tid; e < g.T * g.C; e += CTCF_THREADS) dp[e] = from_f32<T>(0.f);       // frames past the input length
-    if (nll >= 1e29f) {        // no alignment fits: +inf cost, no gradient (see k_ctc)
+    if (nll >= -kDead) {        // no alignment fits: +inf cost, no gradient (see k_ctc)
         for (int e = tid; e < Tn * g.C; e += CTCF_THREADS) dp[e] = from_f32<T>(0.f);
         return;
     }
@@ -308,7 +294,7 @@ k_ctc_fast(const T *__restrict__ pred, const int *__restrict__ labels, const int
             for (int st = 0; st < S; ++st) {
                 if (cls_l[st] != c) continue;
                 const float a = al[(long long)t * g.Smax + st], bt = be[(long long)t * g.Smax + st];
-                if (a > -1e29f && bt > -1e29f) oc += __expf(a + bt - lpt[e] + nll);
+                if (a > kDead && bt > kDead) oc += __expf(a + bt - lpt[e] + nll);
             }
             occ[e] = oc;
         }
@@ -320,7 +306,7 @@ k_ctc_fast(const T *__restrict__ pred, const int *__restrict__ labels, const int
         if (st < S) {
             c = cls_l[st];
             const float a = al[(long long)t * g.Smax + st], bt = be[(long long)t * g.Smax + st];
-            if (a > -1e29f && bt > -1e29f) q = __expf(a + bt - lpt[t * g.C + c] + nll);       // both hold frame t's emission
+            if (a > kDead && bt > kDead) q = __expf(a + bt - lpt[t * g.C + c] + nll);       // both hold frame t's emission
         }
         float qb = (st & 1) ? 0.f : q;               // blanks: half of the states, one class -- reduce inside the wave
 #pragma unroll
@@ -336,6 +322,21 @@ k_ctc_fast(const T *__restrict__ pred, const int *__restrict__ labels, const int
     }
 }
 
+// The fast form of one element type.  A device that refuses the LDS size, or a launch that fails, is no error: false, and the two-sweep
+// kernel takes the call (the memo of this device is reset, so that the next call asks again).
+template <typename TT>
+bool launch_fast(const void *pred, const int *labels, const int *in_len, const int *lab_len, float *cost, void *dpred, float *ws,
+                 float *beta_ws, const CtcGeom &g, size_t lds, hipStream_t stream)
+{
+    static std::atomic<int> granted[kMaxLdsDevices];
+    if (!grant_dynamic_lds(reinterpret_cast<const void *>(&k_ctc_fast<TT>), lds, granted)) { (void)hipGetLastError(); return false; }
+    hipLaunchKernelGGL((k_ctc_fast<TT>), dim3((unsigned)g.B), dim3(CTCF_THREADS), lds, stream, (const TT *)pred, labels, in_len, lab_len,
+                       cost, (TT *)dpred, ws, beta_ws, g);
+    if (hipGetLastError() == hipSuccess) return true;
+    granted[lds_device()].store(0, std::memory_order_relaxed);
+    return false;
+}
+
 }  // namespace
 
 size_t ctc_workspace_bytes(int B, int T, int Lmax) { return 2 * (size_t)B * T * (2 * Lmax + 1) * sizeof(float); }   // alpha and beta lattices
@@ -349,46 +350,27 @@ int launch_ctc(int dtype, int B, int T, int C, const void *pred, const int *labe
     const size_t base = (size_t)(T + 4 * g.Smax + 2 * C + 4) * sizeof(float);
     const size_t full = base + (size_t)T * C * sizeof(float);
     if (g.Smax > CTC_THREADS || C > CTC_THREADS || base > 64 * 1024) return QK_ERR_UNSUPPORTED;
+    if (!dtype_known(dtype)) return QK_ERR_INVALID_ARG;          // (qk_ctc_batch_cost leaves the dtype to this check)
     // fast form: both tables (log-probabilities, occupancies) of the sample in LDS
     const size_t fast_lds = (size_t)(T + 5 * g.Smax + 4 + 2 * (size_t)T * C) * sizeof(float);
     if (fast_lds <= 150 * 1024 && !(debug_flags() & kDbgCtcTwoSweeps)) {
-        float *beta_ws = ws + (size_t)B * T * g.Smax;
-        dim3 grid((unsigned)B), block(CTCF_THREADS);
-        // More than 64 KB of dynamic LDS must be asked for explicitly.  The largest size granted so far is remembered per DEVICE and
-        // element type (the attribute belongs to the device's copy of the function): the attribute call is made only when a call
-        // needs more.  A device that refuses the size, or a launch of the fast form that fails, is no error: the two-sweep kernel
-        // below takes the call.
-        bool fast_ok = true;
-        constexpr int kMaxDevices = 64;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) { (void)hipGetLastError(); dev = 0; }
-#define QK_CTCF(TT) do { static std::atomic<int> granted[kMaxDevices]; \
-        if ((int)fast_lds > granted[dev].load(std::memory_order_relaxed)) { \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ctc_fast<TT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast_lds) == hipSuccess) \
-                granted[dev].store((int)fast_lds, std::memory_order_relaxed); \
-            else { (void)hipGetLastError(); fast_ok = false; } } \
-        if (fast_ok) { hipLaunchKernelGGL((k_ctc_fast<TT>), grid, block, fast_lds, stream, (const TT *)pred, labels, in_len, lab_len, cost, (TT *)dpred, ws, beta_ws, g); \
-            if (hipGetLastError() != hipSuccess) { granted[dev].store(0, std::memory_order_relaxed); fast_ok = false; } } } while (0)
-        switch (dtype) {
-        case QK_F32: QK_CTCF(float); break;
-        case QK_BF16: QK_CTCF(bf16); break;
-        case QK_F16: QK_CTCF(f16); break;
-        default: return QK_ERR_INVALID_ARG;
-        }
-#undef QK_CTCF
+        bool fast_ok = false;
+        by_dtype(dtype, [&](auto t) {
+            fast_ok = launch_fast<decltype(t)>(pred, labels, in_len, lab_len, cost, dpred, ws, ws + (size_t)B * T * g.Smax, g, fast_lds, stream);
+        });
         if (fast_ok) return 0;
     }
     const bool lps = full <= 64 * 1024;
     const size_t lds = lps ? full : base;
-    dim3 grid((unsigned)B), block(CTC_THREADS);
-#define QK_CTC(TT, L) hipLaunchKernelGGL((k_ctc<TT, L>), grid, block, lds, stream, (const TT *)pred, labels, in_len, lab_len, cost, (TT *)dpred, ws, g)
-    switch (dtype) {
-    case QK_F32: if (lps) QK_CTC(float, true); else QK_CTC(float, false); break;
-    case QK_BF16: if (lps) QK_CTC(bf16, true); else QK_CTC(bf16, false); break;
-    case QK_F16: if (lps) QK_CTC(f16, true); else QK_CTC(f16, false); break;
-    default: return QK_ERR_INVALID_ARG;
-    }
-#undef QK_CTC
+    by_dtype(dtype, [&](auto t) {
+        using TT = decltype(t);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(CTC_THREADS), lds, stream, (const TT *)pred, labels, in_len, lab_len, cost,
+                               (TT *)dpred, ws, g);
+        };
+        if (lps) launch(k_ctc<TT, true>);
+        else launch(k_ctc<TT, false>);
+    });
     return hipGetLastError() == hipSuccess ? 0 : QK_ERR_LAUNCH;
 }
 

@@ -16,18 +16,17 @@
 //     starts and ends are then written by all threads, the -1 fill included.
 // Every LDS and global index is bounded by the clamped Tn, Ln and S, never by a raw input value: back-pointers are 0, 1 or 2 by
 // construction and the backtrack clamps the state at 0 all the same.
-#include "qk_common.h"
-#include <atomic>
+#include "qk_ctc_lattice.h"
+#include "qk_seq.h"
 
 namespace qk {
 namespace {
 
-constexpr float kNegInf = -1e30f;
 constexpr int ALIGN_THREADS = 256;
 constexpr int ALIGN_WAVES = ALIGN_THREADS / 64;
 constexpr size_t kAlignLdsBudget = 150 * 1024;        // of the CU's 160 KB; above 64 KB the launcher asks for it explicitly
 
-struct AlignGeom { int B, T, C, Lmax, Smax; float eps; };
+struct AlignGeom : LatticeGeom {};         // (its own name: the name is part of the kernels' symbols)
 
 // LDS image, in this order (the 64-bit words first: they need 8-byte alignment):
 //   bp[T][4 waves][2] u64 (BPL) | v[2][Smax] f32 | lse[T] f32 | cls[Smax] i32 | red[4] f32, flag[4] i32 | u[T][C] f32 (LPS) | state[T] u8
@@ -112,7 +111,7 @@ k_ctc_align(const T *__restrict__ pred, const int *__restrict__ labels, const in
             float best = ap[s];                         // ties: stay, then s - 1, then s - 2 -- strict comparisons; -inf never wins
             if (s >= 1) { const float a1 = ap[s - 1]; if (a1 > best) { best = a1; back = 1; } }
             if (skip_ok) { const float a2 = ap[s - 2]; if (a2 > best) { best = a2; back = 2; } }
-            an[s] = best <= -1e29f ? kNegInf : best + e_cur;
+            an[s] = best <= kDead ? kNegInf : best + e_cur;
         }
         const unsigned long long lo = __ballot(back & 1), hi = __ballot(back >> 1);
         if (wave_live && lane == 0) {
@@ -129,7 +128,7 @@ k_ctc_align(const T *__restrict__ pred, const int *__restrict__ labels, const in
         int st = S - 1;
         float best = al[S - 1];
         if (S >= 2 && al[S - 2] > best) { best = al[S - 2]; st = S - 2; }        // S - 1 wins a tie
-        const int feasible = best > -1e29f ? 1 : 0;
+        const int feasible = best > kDead ? 1 : 0;
         if (feasible) {
             pst[Tn - 1] = (unsigned char)st;
             for (int t = Tn - 1; t >= 1; --t) {
@@ -170,38 +169,19 @@ k_ctc_align(const T *__restrict__ pred, const int *__restrict__ labels, const in
     if (tid == 0) score[b] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// One form of one element type.  1: the device refuses the LDS size, and the caller takes a form that needs less.
 template <typename TT, bool LPS, bool BPL>
 int launch_form(const void *pred, const int *labels, const int *in_len, const int *lab_len, int *path, int *starts, int *ends, float *score,
                 void *ws, const AlignGeom &g, size_t lds, hipStream_t stream)
 {
-    // More than 64 KB of dynamic LDS must be asked for explicitly; the largest size granted is remembered per device (as in launch_ctc).
-    if (lds > 64 * 1024) {
-        constexpr int kMaxDevices = 64;
-        static std::atomic<int> granted[kMaxDevices];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) { (void)hipGetLastError(); dev = 0; }
-        if ((int)lds > granted[dev].load(std::memory_order_relaxed)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ctc_align<TT, LPS, BPL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds) != hipSuccess) {
-                (void)hipGetLastError();
-                return 1;                      // refused: the caller takes a form that needs less
-            }
-            granted[dev].store((int)lds, std::memory_order_relaxed);
-        }
+    static std::atomic<int> granted[kMaxLdsDevices];
+    if (lds > 64 * 1024 && !grant_dynamic_lds(reinterpret_cast<const void *>(&k_ctc_align<TT, LPS, BPL>), lds, granted)) {
+        (void)hipGetLastError();
+        return 1;
     }
     hipLaunchKernelGGL((k_ctc_align<TT, LPS, BPL>), dim3((unsigned)g.B), dim3(ALIGN_THREADS), lds, stream, (const TT *)pred, labels, in_len,
                        lab_len, path, starts, ends, score, static_cast<unsigned long long *>(ws), g);
     return hipGetLastError() == hipSuccess ? 0 : QK_ERR_LAUNCH;
-}
-
-template <typename TT>
-int launch_dtype(bool lps, bool bpl, const void *pred, const int *labels, const int *in_len, const int *lab_len, int *path, int *starts,
-                 int *ends, float *score, void *ws, const AlignGeom &g, size_t lds, hipStream_t stream)
-{
-#define QK_ALIGN_FORM(L, P) launch_form<TT, L, P>(pred, labels, in_len, lab_len, path, starts, ends, score, ws, g, lds, stream)
-    if (lps) return bpl ? QK_ALIGN_FORM(true, true) : QK_ALIGN_FORM(true, false);
-    return bpl ? QK_ALIGN_FORM(false, true) : QK_ALIGN_FORM(false, false);
-#undef QK_ALIGN_FORM
 }
 
 }  // namespace
@@ -216,7 +196,7 @@ bool ctc_align_supported(int T, int C, int Lmax)
 int launch_ctc_align(int dtype, int B, int T, int C, const void *pred, const int *labels, int Lmax, const int *in_len, const int *lab_len,
                      int *path, int *starts, int *ends, float *score, void *ws, hipStream_t stream)
 {
-    if (!ctc_align_supported(T, C, Lmax)) return QK_ERR_UNSUPPORTED;
+    if (!ctc_align_supported(T, C, Lmax) || !dtype_known(dtype)) return QK_ERR_UNSUPPORTED;
     AlignGeom g;
     g.B = B; g.T = T; g.C = C; g.Lmax = Lmax; g.Smax = 2 * Lmax + 1; g.eps = 1e-7f;
     // forms in order of preference: back-pointers and table in LDS, back-pointers only, table only, neither
@@ -226,13 +206,13 @@ int launch_ctc_align(int dtype, int B, int T, int C, const void *pred, const int
         const bool lps = kForms[f][0], bpl = kForms[f][1];
         const size_t lds = align_lds_bytes(T, C, g.Smax, lps, bpl);
         if (lds > budget) continue;
-        int rc;
-        switch (dtype) {
-        case QK_F32: rc = launch_dtype<float>(lps, bpl, pred, labels, in_len, lab_len, path, starts, ends, score, ws, g, lds, stream); break;
-        case QK_BF16: rc = launch_dtype<bf16>(lps, bpl, pred, labels, in_len, lab_len, path, starts, ends, score, ws, g, lds, stream); break;
-        case QK_F16: rc = launch_dtype<f16>(lps, bpl, pred, labels, in_len, lab_len, path, starts, ends, score, ws, g, lds, stream); break;
-        default: return QK_ERR_UNSUPPORTED;
-        }
+        int rc = 0;
+        by_dtype(dtype, [&](auto t) {
+            using TT = decltype(t);
+            static constexpr decltype(&launch_form<TT, true, true>) kLaunch[2][2] = {      // [lps][bpl]
+                {&launch_form<TT, false, false>, &launch_form<TT, false, true>}, {&launch_form<TT, true, false>, &launch_form<TT, true, true>}};
+            rc = kLaunch[lps][bpl](pred, labels, in_len, lab_len, path, starts, ends, score, ws, g, lds, stream);
+        });
         if (rc != 1) return rc;
         budget = 64 * 1024;                    // the device grants no more than the default: a smaller form of the same kernel
     }

@@ -18,7 +18,7 @@
 //                    re-ranked by S + alpha log P(</s> | prefix) by a counting rank before the backtrack.
 //   k_edit_distance  one wave per pair: Levenshtein distance row by row over the hypothesis, vectorised over the reference, the
 //                    insertion chain along a row as a wave prefix-min: D[j] = j + min_{k <= j} (tmp[k] - k).
-#include "qk_common.h"
+#include "qk_seq.h"
 #include <climits>
 
 namespace qk {
@@ -575,13 +575,11 @@ int launch_ctc_greedy(int dtype, int B, int T, int C, const void *pred, const in
                       hipStream_t stream)
 {
     if (C < 2 || C > kMaxClasses) return QK_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)B), block(64);
-    switch (dtype) {
-    case QK_F32: hipLaunchKernelGGL(k_ctc_greedy<float>, grid, block, 0, stream, (const float *)pred, in_len, B, T, C, decoded, dlen, logp); break;
-    case QK_BF16: hipLaunchKernelGGL(k_ctc_greedy<bf16>, grid, block, 0, stream, (const bf16 *)pred, in_len, B, T, C, decoded, dlen, logp); break;
-    case QK_F16: hipLaunchKernelGGL(k_ctc_greedy<f16>, grid, block, 0, stream, (const f16 *)pred, in_len, B, T, C, decoded, dlen, logp); break;
-    default: return QK_ERR_INVALID_ARG;
-    }
+    if (!dtype_known(dtype)) return QK_ERR_INVALID_ARG;
+    by_dtype(dtype, [&](auto t) {
+        using TT = decltype(t);
+        hipLaunchKernelGGL(k_ctc_greedy<TT>, dim3((unsigned)B), dim3(64), 0, stream, (const TT *)pred, in_len, B, T, C, decoded, dlen, logp);
+    });
     return hipGetLastError() == hipSuccess ? 0 : QK_ERR_LAUNCH;
 }
 
@@ -591,14 +589,13 @@ int launch_ctc_beam(int dtype, int B, int T, int C, const void *pred, const int 
     if (C < 2 || C > kMaxClasses || W < 1 || W > kMaxBeam || top < 1 || top > W) return QK_ERR_UNSUPPORTED;
     BeamGeom g;
     g.B = B; g.T = T; g.C = C; g.W = W; g.top = top; g.merge = merge ? 1 : 0;
+    if (!dtype_known(dtype)) return QK_ERR_INVALID_ARG;
     LmGeom lm = {};
-    dim3 grid((unsigned)B), block(BEAM_THREADS);
-    switch (dtype) {
-    case QK_F32: hipLaunchKernelGGL((k_ctc_beam<float, false>), grid, block, 0, stream, (const float *)pred, in_len, g, lm, decoded, dlen, logp, hist); break;
-    case QK_BF16: hipLaunchKernelGGL((k_ctc_beam<bf16, false>), grid, block, 0, stream, (const bf16 *)pred, in_len, g, lm, decoded, dlen, logp, hist); break;
-    case QK_F16: hipLaunchKernelGGL((k_ctc_beam<f16, false>), grid, block, 0, stream, (const f16 *)pred, in_len, g, lm, decoded, dlen, logp, hist); break;
-    default: return QK_ERR_INVALID_ARG;
-    }
+    by_dtype(dtype, [&](auto t) {
+        using TT = decltype(t);
+        hipLaunchKernelGGL((k_ctc_beam<TT, false>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, stream, (const TT *)pred, in_len, g, lm, decoded,
+                           dlen, logp, hist);
+    });
     return hipGetLastError() == hipSuccess ? 0 : QK_ERR_LAUNCH;
 }
 
@@ -615,6 +612,7 @@ int launch_ctc_beam_lm(int dtype, int B, int T, int C, const void *pred, const i
 {
     if (C < 2 || C > kMaxClasses || W < 1 || W > kMaxBeam || top < 1 || top > W || !ctc_beam_lm_supported(C, W, order))
         return QK_ERR_UNSUPPORTED;
+    if (!dtype_known(dtype)) return QK_ERR_INVALID_ARG;
     BeamGeom g;
     g.B = B; g.T = T; g.C = C; g.W = W; g.top = top; g.merge = merge ? 1 : 0;
     LmGeom lm;
@@ -622,21 +620,16 @@ int launch_ctc_beam_lm(int dtype, int B, int T, int C, const void *pred, const i
     lm.use_tab = alpha != 0.f;
     lm.whole = lm_lds_bytes(C, W, order, true, true) - kLmHeadWords * sizeof(float) <= kLmWholeTableBytes;
     const size_t lds = lm_lds_bytes(C, W, order, lm.whole, lm.use_tab);
-    dim3 grid((unsigned)B), block(BEAM_THREADS);
-#define QK_BEAM_LM(TT)                                                                                                                  \
-    do {                                                                                                                                \
-        if (lds > 65536 && hipFuncSetAttribute((const void *)k_ctc_beam<TT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                               (int)lds) != hipSuccess)                                                                 \
-            return QK_ERR_LAUNCH;                                                                                                       \
-        hipLaunchKernelGGL((k_ctc_beam<TT, true>), grid, block, lds, stream, (const TT *)pred, in_len, g, lm, decoded, dlen, logp, hist); \
-    } while (0)
-    switch (dtype) {
-    case QK_F32: QK_BEAM_LM(float); break;
-    case QK_BF16: QK_BEAM_LM(bf16); break;
-    case QK_F16: QK_BEAM_LM(f16); break;
-    default: return QK_ERR_INVALID_ARG;
-    }
-#undef QK_BEAM_LM
+    bool granted_ok = true;
+    by_dtype(dtype, [&](auto t) {
+        using TT = decltype(t);
+        static std::atomic<int> granted[kMaxLdsDevices];
+        granted_ok = lds <= 65536 || grant_dynamic_lds(reinterpret_cast<const void *>(&k_ctc_beam<TT, true>), lds, granted);
+        if (granted_ok)
+            hipLaunchKernelGGL((k_ctc_beam<TT, true>), dim3((unsigned)B), dim3(BEAM_THREADS), lds, stream, (const TT *)pred, in_len, g, lm,
+                               decoded, dlen, logp, hist);
+    });
+    if (!granted_ok) return QK_ERR_LAUNCH;         // (HIP's error of the refusal is what the entry point reports)
     return hipGetLastError() == hipSuccess ? 0 : QK_ERR_LAUNCH;
 }
 

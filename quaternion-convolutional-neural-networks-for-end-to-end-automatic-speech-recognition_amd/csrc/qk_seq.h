@@ -1,7 +1,8 @@
 // What the sequence kernels (qk_qlstm.hip, qk_qlnorm.hip, qk_qattn.hip, qk_qdwconv.hip, qk_rnnt.hip) share: 16-byte register groups,
 // the 16x16x32 MFMA of both 16-bit types, and the host-side checks of their entry points.  Only helpers that are the SAME code in
 // every file live here; what differs in arithmetic or evaluation order stays in its file ("The sequence kernels' shared
-// header").
+// header").  The CTC files (qk_ctc.hip, qk_ctc_align.hip, qk_ctc_decode.hip) and qk_api.hip use the host side only: the dtype
+// dispatch and the argument checks.
 #pragma once
 
 #include "qk_common.h"

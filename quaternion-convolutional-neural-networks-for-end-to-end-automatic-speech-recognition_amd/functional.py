@@ -1285,28 +1285,33 @@ def weighted_sum(a, w):
     return _WeightedSumFn.apply(a.contiguous(), w.contiguous())
 
 
+def _ctc_call(y_pred, labels, input_length, label_length, want_grad):
+    """qk_ctc_batch_cost on a contiguous device y_pred (B, T, C): (cost (B,), d cost / d y_pred or None), one launch."""
+    b, t, c = y_pred.shape
+    lab = labels.to(device=y_pred.device, dtype=torch.int32).contiguous()
+    il = input_length.reshape(-1).to(device=y_pred.device, dtype=torch.int32).contiguous()
+    ll = label_length.reshape(-1).to(device=y_pred.device, dtype=torch.int32).contiguous()
+    lmax = lab.shape[1] if lab.dim() == 2 else 0
+    cost = torch.empty(b, dtype=torch.float32, device=y_pred.device)
+    dpred = torch.empty_like(y_pred) if want_grad else None
+    n = int(L.lib().qk_ctc_workspace_bytes(b, t, lmax))
+    ws = torch.empty(n, dtype=torch.uint8, device=y_pred.device)
+    with _on_device(y_pred.device):
+        rc = L.lib().qk_ctc_batch_cost(_DTYPES[y_pred.dtype], b, t, c, _ptr(y_pred), _ptr(lab), lmax, _ptr(il), _ptr(ll), _ptr(cost),
+                                       _ptr(dpred), _ptr(ws), n, _stream(y_pred))
+    L.check(rc, 'qk_ctc_batch_cost')
+    return cost, dpred
+
+
 class _CtcFn(torch.autograd.Function):
     """qk_ctc_batch_cost: cost and d cost / d y_pred from one launch; the backward only scales the stored gradient."""
 
     @staticmethod
     def forward(ctx, y_pred, labels, input_length, label_length, loss_scale=1.0):
-        b, t, c = y_pred.shape
-        lab = labels.to(device=y_pred.device, dtype=torch.int32).contiguous()
-        il = input_length.reshape(-1).to(device=y_pred.device, dtype=torch.int32).contiguous()
-        ll = label_length.reshape(-1).to(device=y_pred.device, dtype=torch.int32).contiguous()
-        lmax = lab.shape[1] if lab.dim() == 2 else 0
-        cost = torch.empty(b, dtype=torch.float32, device=y_pred.device)
-        want = ctx.needs_input_grad[0]
-        dpred = torch.empty_like(y_pred) if want else None
-        n = int(L.lib().qk_ctc_workspace_bytes(b, t, lmax))
-        ws = torch.empty(n, dtype=torch.uint8, device=y_pred.device)
-        with _on_device(y_pred.device):
-            rc = L.lib().qk_ctc_batch_cost(_DTYPES[y_pred.dtype], b, t, c, _ptr(y_pred), _ptr(lab), lmax, _ptr(il), _ptr(ll), _ptr(cost),
-                                           _ptr(dpred), _ptr(ws), n, _stream(y_pred))
-        L.check(rc, 'qk_ctc_batch_cost')
+        cost, dpred = _ctc_call(y_pred, labels, input_length, label_length, ctx.needs_input_grad[0])
         ctx.save_for_backward(dpred)
         ctx.loss_scale = loss_scale if isinstance(loss_scale, torch.Tensor) else float(loss_scale)
-        return cost.reshape(b, 1)
+        return cost.reshape(-1, 1)
 
     @staticmethod
     def backward(ctx, dcost):
@@ -1321,21 +1326,7 @@ def ctc_cost_and_grad(y_pred, labels, input_length, label_length):
     """(cost (B,), d cost / d y_pred) of qk_ctc_batch_cost as plain tensors (no autograd node): for callers that chain the gradient
     themselves (layers._DenseSoftmaxCtcMeanFn)."""
     _require_device(y_pred, 'ctc_cost_and_grad')
-    y_pred = y_pred.contiguous()
-    b, t, c = y_pred.shape
-    lab = labels.to(device=y_pred.device, dtype=torch.int32).contiguous()
-    il = input_length.reshape(-1).to(device=y_pred.device, dtype=torch.int32).contiguous()
-    ll = label_length.reshape(-1).to(device=y_pred.device, dtype=torch.int32).contiguous()
-    lmax = lab.shape[1] if lab.dim() == 2 else 0
-    cost = torch.empty(b, dtype=torch.float32, device=y_pred.device)
-    dpred = torch.empty_like(y_pred)
-    n = int(L.lib().qk_ctc_workspace_bytes(b, t, lmax))
-    ws = torch.empty(n, dtype=torch.uint8, device=y_pred.device)
-    with _on_device(y_pred.device):
-        rc = L.lib().qk_ctc_batch_cost(_DTYPES[y_pred.dtype], b, t, c, _ptr(y_pred), _ptr(lab), lmax, _ptr(il), _ptr(ll), _ptr(cost),
-                                       _ptr(dpred), _ptr(ws), n, _stream(y_pred))
-    L.check(rc, 'qk_ctc_batch_cost')
-    return cost, dpred
+    return _ctc_call(y_pred.contiguous(), labels, input_length, label_length, True)
 
 
 def ctc_shape_supported(frames, classes, max_label_len):
@@ -1449,6 +1440,17 @@ def rnnt_loss(logits, labels, input_length, label_length, loss_scale=1.0):
 CTC_MAX_BEAM, CTC_MAX_CLASSES, EDIT_MAX_REF = 128, 256, 1024
 
 
+def _length_arg(v, b, device, what, name):
+    """A (B,) or (B, 1) length argument, checked (shapes first: a bad shape is refused on any device) but not yet moved."""
+    if not torch.is_tensor(v):
+        v = torch.as_tensor(v)
+    if v.numel() != b or (v.dim() == 2 and v.shape[1] != 1) or v.dim() > 2:
+        raise ValueError('%s: %s must have shape (B,) or (B, 1), got %s' % (what, name, tuple(v.shape)))
+    if v.is_cuda and v.device != device:
+        raise ValueError('%s: %s is on %s, y_pred on %s' % (what, name, v.device, device))
+    return v.reshape(-1)
+
+
 def _decode_args(y_pred, input_length, what):
     _require_device(y_pred, what)
     if y_pred.dim() != 3 or min(y_pred.shape) < 1:
@@ -1456,15 +1458,27 @@ def _decode_args(y_pred, input_length, what):
     b, t, c = y_pred.shape
     if c < 2 or c > CTC_MAX_CLASSES:
         raise ValueError('%s: %d classes; the decoders take 2 <= classes <= %d' % (what, c, CTC_MAX_CLASSES))
-    il = input_length
-    if not torch.is_tensor(il):
-        il = torch.as_tensor(il)
-    if il.numel() != b or (il.dim() == 2 and il.shape[1] != 1) or il.dim() > 2:
-        raise ValueError('%s: input_length must have shape (B,) or (B, 1), got %s' % (what, tuple(il.shape)))
-    if il.is_cuda and il.device != y_pred.device:
-        raise ValueError('%s: input_length is on %s, y_pred on %s' % (what, il.device, y_pred.device))
-    il = il.reshape(-1).to(device=y_pred.device, dtype=torch.int32).contiguous()
-    return y_pred.contiguous(), il
+    il = _length_arg(input_length, b, y_pred.device, what, 'input_length')
+    return y_pred.contiguous(), il.to(device=y_pred.device, dtype=torch.int32).contiguous()
+
+
+def _beam_args(what, beam_width, top_paths):
+    beam_width, top_paths = int(beam_width), int(top_paths)
+    if not 1 <= beam_width <= CTC_MAX_BEAM:
+        raise ValueError('%s: beam_width %d outside 1 .. %d' % (what, beam_width, CTC_MAX_BEAM))
+    if not 1 <= top_paths <= beam_width:
+        raise ValueError('%s: top_paths %d outside 1 .. beam_width (%d)' % (what, top_paths, beam_width))
+    return beam_width, top_paths
+
+
+def _beam_buffers(y, beam_width, top_paths):
+    """(decoded, decoded_len, log_prob, workspace) of a beam search over y (B, T, C)."""
+    b, t, _ = y.shape
+    dec = torch.empty((top_paths, b, t), dtype=torch.int32, device=y.device)
+    dlen = torch.empty((top_paths, b), dtype=torch.int32, device=y.device)
+    lp = torch.empty((b, top_paths), dtype=torch.float32, device=y.device)
+    ws = torch.empty(int(L.lib().qk_ctc_beam_workspace_bytes(b, t, beam_width)), dtype=torch.uint8, device=y.device)
+    return dec, dlen, lp, ws
 
 
 def ctc_greedy_decode(y_pred, input_length):
@@ -1498,21 +1512,13 @@ def ctc_beam_search_decode(y_pred, input_length, beam_width=100, top_paths=1, me
     per frame); paths beyond the number of distinct beams come back empty with log_prob -inf (TensorFlow raises).
     merge_repeated (True, the TF 1.x default Keras 2.x calls) collapses consecutive equal labels of the returned prefix; log_prob stays
     that of the uncollapsed prefix.  Limits: beam_width <= 128, top_paths <= beam_width, C <= 256."""
-    beam_width, top_paths = int(beam_width), int(top_paths)
-    if not 1 <= beam_width <= CTC_MAX_BEAM:
-        raise ValueError('ctc_beam_search_decode: beam_width %d outside 1 .. %d' % (beam_width, CTC_MAX_BEAM))
-    if not 1 <= top_paths <= beam_width:
-        raise ValueError('ctc_beam_search_decode: top_paths %d outside 1 .. beam_width (%d)' % (top_paths, beam_width))
+    beam_width, top_paths = _beam_args('ctc_beam_search_decode', beam_width, top_paths)
     y, il = _decode_args(y_pred, input_length, 'ctc_beam_search_decode')
     b, t, c = y.shape
-    dec = torch.empty((top_paths, b, t), dtype=torch.int32, device=y.device)
-    dlen = torch.empty((top_paths, b), dtype=torch.int32, device=y.device)
-    lp = torch.empty((b, top_paths), dtype=torch.float32, device=y.device)
-    n = int(L.lib().qk_ctc_beam_workspace_bytes(b, t, beam_width))
-    ws = torch.empty(n, dtype=torch.uint8, device=y.device)
+    dec, dlen, lp, ws = _beam_buffers(y, beam_width, top_paths)
     with _on_device(y.device):
         rc = L.lib().qk_ctc_beam_search_decode(_DTYPES[y.dtype], b, t, c, _ptr(y), _ptr(il), beam_width, top_paths, int(bool(merge_repeated)),
-                                               _ptr(dec), _ptr(dlen), _ptr(lp), _ptr(ws), n, _stream(y))
+                                               _ptr(dec), _ptr(dlen), _ptr(lp), _ptr(ws), ws.numel(), _stream(y))
     L.check(rc, 'qk_ctc_beam_search_decode')
     return dec, dlen, lp
 
@@ -1520,17 +1526,6 @@ def ctc_beam_search_decode(y_pred, input_length, beam_width=100, top_paths=1, me
 # ---- CTC forced alignment (include/qk.h, "CTC forced alignment") ---------------------------------------------------------------------
 CTC_ALIGN_MAX_LABELS = 127
 AlignResult = collections.namedtuple('AlignResult', 'path starts ends score')
-
-
-def _length_arg(v, b, device, what, name):
-    """A (B,) or (B, 1) length argument, checked (shapes first: a bad shape is refused on any device) but not yet moved."""
-    if not torch.is_tensor(v):
-        v = torch.as_tensor(v)
-    if v.numel() != b or (v.dim() == 2 and v.shape[1] != 1) or v.dim() > 2:
-        raise ValueError('%s: %s must have shape (B,) or (B, 1), got %s' % (what, name, tuple(v.shape)))
-    if v.is_cuda and v.device != device:
-        raise ValueError('%s: %s is on %s, y_pred on %s' % (what, name, v.device, device))
-    return v.reshape(-1)
 
 
 def ctc_forced_align(y_pred, labels, input_length, label_length):
@@ -1594,11 +1589,7 @@ def ctc_beam_search_decode_lm(y_pred, input_length, lm, beam_width=100, top_path
     acoustic log p(prefix | y_pred), score (B, top_paths) float32 = the S the paths were ranked by), without a host sync; empty paths
     have -inf in both.  merge_repeated collapses the output; the LM scored the uncollapsed prefix."""
     what = 'ctc_beam_search_decode_lm'
-    beam_width, top_paths = int(beam_width), int(top_paths)
-    if not 1 <= beam_width <= CTC_MAX_BEAM:
-        raise ValueError('%s: beam_width %d outside 1 .. %d' % (what, beam_width, CTC_MAX_BEAM))
-    if not 1 <= top_paths <= beam_width:
-        raise ValueError('%s: top_paths %d outside 1 .. beam_width (%d)' % (what, top_paths, beam_width))
+    beam_width, top_paths = _beam_args(what, beam_width, top_paths)
     lm_weight, insertion_bonus = float(lm_weight), float(insertion_bonus)
     if not (math.isfinite(lm_weight) and lm_weight >= 0.0):
         raise ValueError('%s: lm_weight must be finite and >= 0, got %r' % (what, lm_weight))
@@ -1619,16 +1610,12 @@ def ctc_beam_search_decode_lm(y_pred, input_length, lm, beam_width=100, top_path
     if tuple(table.shape) != (c ** (order - 1), c) or table.dtype != torch.float32:
         raise ValueError('%s: LM table of shape %s %s, expected (%d, %d) float32' % (what, tuple(table.shape), table.dtype,
                                                                                      c ** (order - 1), c))
-    dec = torch.empty((top_paths, b, t), dtype=torch.int32, device=y.device)
-    dlen = torch.empty((top_paths, b), dtype=torch.int32, device=y.device)
-    lp = torch.empty((b, top_paths), dtype=torch.float32, device=y.device)
-    score = torch.empty((b, top_paths), dtype=torch.float32, device=y.device)
-    n = int(L.lib().qk_ctc_beam_workspace_bytes(b, t, beam_width))
-    ws = torch.empty(n, dtype=torch.uint8, device=y.device)
+    dec, dlen, lp, ws = _beam_buffers(y, beam_width, top_paths)
+    score = torch.empty_like(lp)
     with _on_device(y.device):
         rc = L.lib().qk_ctc_beam_search_decode_lm(_DTYPES[y.dtype], b, t, c, _ptr(y), _ptr(il), beam_width, top_paths,
                                                   int(bool(merge_repeated)), order, _ptr(table), lm_weight, insertion_bonus,
-                                                  int(bool(eos)), _ptr(dec), _ptr(dlen), _ptr(lp), _ptr(score), _ptr(ws), n, _stream(y))
+                                                  int(bool(eos)), _ptr(dec), _ptr(dlen), _ptr(lp), _ptr(score), _ptr(ws), ws.numel(), _stream(y))
     L.check(rc, 'qk_ctc_beam_search_decode_lm')
     return dec, dlen, lp, score
 
@@ -1647,23 +1634,35 @@ def _token_args(seq, length, what, name):
             ln.reshape(-1).to(device=seq.device, dtype=torch.int32).contiguous())
 
 
-def _edit_distance(hyp, hyp_len, ref, ref_len, class_map=None):
-    what = 'edit_distance'
+def _pair_args(what, hyp, hyp_len, ref, ref_len, class_map, between=None):
+    """(hyp, hyp_len, ref, ref_len, class_map or None, classes) of a scoring call as int32 device tensors: the two token arguments,
+    their devices, then between(hyp, ref) -- the caller's own checks, which come before the class map's -- then the class map."""
     h, hl = _token_args(hyp, hyp_len, what, 'hyp')
     r, rl = _token_args(ref, ref_len, what, 'ref')
     if h.device != r.device:
         raise ValueError('%s: hyp on %s, ref on %s' % (what, h.device, r.device))
-    if h.shape[0] != r.shape[0]:
-        raise ValueError('%s: %d hypotheses, %d references' % (what, h.shape[0], r.shape[0]))
-    if r.shape[1] > EDIT_MAX_REF:
-        raise ValueError('%s: references of up to %d tokens are supported, got %d' % (what, EDIT_MAX_REF, r.shape[1]))
-    b = h.shape[0]
+    if between is not None:
+        between(h, r)
     cm, classes = None, 0
     if class_map is not None:
         cm = torch.as_tensor(class_map).reshape(-1).to(device=h.device, dtype=torch.int32).contiguous()
         classes = cm.numel()
         if classes < 1:
             raise ValueError('%s: empty class_map' % what)
+    return h, hl, r, rl, cm, classes
+
+
+def _edit_distance(hyp, hyp_len, ref, ref_len, class_map=None):
+    what = 'edit_distance'
+
+    def shapes(h, r):
+        if h.shape[0] != r.shape[0]:
+            raise ValueError('%s: %d hypotheses, %d references' % (what, h.shape[0], r.shape[0]))
+        if r.shape[1] > EDIT_MAX_REF:
+            raise ValueError('%s: references of up to %d tokens are supported, got %d' % (what, EDIT_MAX_REF, r.shape[1]))
+
+    h, hl, r, rl, cm, classes = _pair_args(what, hyp, hyp_len, ref, ref_len, class_map, shapes)
+    b = h.shape[0]
     dist = torch.empty(b, dtype=torch.int32, device=h.device)
     rlen = torch.empty(b, dtype=torch.int32, device=h.device)
     if b == 0:
@@ -1715,19 +1714,12 @@ def edit_alignment(hyp, hyp_len, ref, ref_len, class_map=None, confusion=None, a
         k = confusion.shape[0] - 1
         if k > EDIT_ALIGN_MAX_CLASSES:
             raise ValueError('%s: a confusion matrix of up to %d classes is supported, got %d' % (what, EDIT_ALIGN_MAX_CLASSES, k))
-    h, hl = _token_args(hyp, hyp_len, what, 'hyp')
-    r, rl = _token_args(ref, ref_len, what, 'ref')
-    if h.device != r.device:
-        raise ValueError('%s: hyp on %s, ref on %s' % (what, h.device, r.device))
-    if confusion is not None and confusion.device != h.device:
-        raise ValueError('%s: confusion on %s, hyp on %s' % (what, confusion.device, h.device))
+    def confusion_device(h, r):
+        if confusion is not None and confusion.device != h.device:
+            raise ValueError('%s: confusion on %s, hyp on %s' % (what, confusion.device, h.device))
+
+    h, hl, r, rl, cm, classes = _pair_args(what, hyp, hyp_len, ref, ref_len, class_map, confusion_device)
     b, a = h.shape[0], h.shape[1] + r.shape[1]
-    cm, classes = None, 0
-    if class_map is not None:
-        cm = torch.as_tensor(class_map).reshape(-1).to(device=h.device, dtype=torch.int32).contiguous()
-        classes = cm.numel()
-        if classes < 1:
-            raise ValueError('%s: empty class_map' % what)
     counts = torch.empty((b, 4), dtype=torch.int32, device=h.device)
     ali_ref = ali_hyp = ali_len = None
     if align:

@@ -99,6 +99,10 @@ CTC_SHAPES = [(3, 9, 2, 4),          # smallest: blank plus one label, repeats o
               (4, 1, 6, 1),          # T = 1 and input_length 0
               (5, 200, 62, 50)]      # the model's own width, ragged
 CTC_BATCH = (256, 200, 62, 50)
+# By launch_ctc's arithmetic neither the fast form ((320 + 5 * 13 + 4 + 2 * 320 * 62) * 4 = 160 276 bytes > 150 KB) nor the table form
+# ((320 + 4 * 13 + 2 * 62 + 4) * 4 + 320 * 62 * 4 = 81 376 bytes > 64 KB) takes it: the two-sweep kernel that gathers its emissions
+# from global memory, with default flags.  Two samples only (see ctc_inputs), so it is not one of CTC_SHAPES.
+CTC_FROM_GLOBAL = (2, 320, 62, 6)
 FAMILIES = ['diffuse', 'peaked']
 _CTC_IN, _CTC_REF = {}, {}
 
@@ -123,7 +127,8 @@ def _alignment(rng, labels, frames, blank):
 
 
 def ctc_inputs(shape, family):
-    """(p64 (B, T, C), labels, input_length, label_length), read-only.  Sample 0 at full length (T frames, Lmax labels) with a repeated
+    """(p64 (B, T, C), labels, input_length, label_length), read-only.  B = 2: sample 0 feasible with a repeated label and an
+    input_length below T, sample 1 infeasible.  Otherwise sample 0 at full length (T frames, Lmax labels) with a repeated
     label; sample 1 without labels; sample 2 infeasible (fewer frames than labels); the others ragged with a repeat.  T = 1: samples
     2 and 3 have input_length 0 (with and without a label).  p = 0.98 softmax(logits) + 0.02 / C, so |g| <= 1 / p <= 50 C;
     'diffuse': logits = 2 randn; 'peaked': the same raised by 4 along a random valid alignment of each feasible sample."""
@@ -144,6 +149,10 @@ def ctc_inputs(shape, family):
     ll = np.zeros(B, dtype=np.int64)
     if T == 1:
         il[:], ll[:] = [1, 1, 0, 0][:B], [1, 0, 1, 0][:B]
+    elif B == 2:
+        ll[:] = Lmax
+        labels[0, 1] = labels[0, 0]
+        il[:] = rng.randint(T // 2, T), max(1, Lmax // 2)
     else:
         for b in range(B):
             if b == 0:
@@ -161,7 +170,9 @@ def ctc_inputs(shape, family):
                 labels[b, k] = labels[b, k - 1]
                 il[b] = rng.randint(_need(labels[b, :ll[b]]), T + 1)
     feasible = np.array([_need(labels[b, :ll[b]]) <= il[b] for b in range(B)])
-    if T > 1:
+    if B == 2:
+        assert feasible[0] and not feasible[1] and il[0] < T and _need(labels[0, :ll[0]]) > ll[0]
+    elif T > 1:
         assert feasible[0] and feasible[1] and not feasible[2] and feasible[3:].all() and il[0] == T and ll[0] == Lmax
         assert _need(labels[0, :ll[0]]) > ll[0]                        # sample 0 does hold a repeated label
     logits = 2.0 * rng.randn(B, T, C)
@@ -626,6 +637,30 @@ def test_ctc_kernels_elementwise(shape, family, kind):
         _note('ctc gradient (%s)' % form, kind, rg)
         if shape == CTC_SHAPES[-1]:
             _note('ctc row sums (%s)' % form, kind, _row_sum_check(g, ref['pred'], ref, kind, what))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('kind', KINDS)
+def test_ctc_two_sweep_kernel_with_emissions_from_global_memory(kind):
+    """The form no shape of CTC_SHAPES selects with default flags: k_ctc<T, false>, whose phase 0 forms log(p + eps) from global
+    memory on both passes of the normaliser and whose sweeps gather every emission one frame ahead.  Reference and bounds as in
+    test_ctc_kernels_elementwise; one sample ends before T, the other is infeasible."""
+    dev = _need_gpu()
+    from qcnn_amd import functional as Fq
+    shape, family = CTC_FROM_GLOBAL, 'diffuse'
+    B, T, C, Lmax = shape
+    S = 2 * Lmax + 1
+    assert (T + 5 * S + 4 + 2 * T * C) * 4 > 150 * 1024 and (T + 4 * S + 2 * C + 4) * 4 + T * C * 4 > 64 * 1024
+    ref = ctc_reference(shape, family, kind)
+    p, labels, il, ll = ctc_inputs(shape, family)
+    assert il[0] < T and np.isfinite(ref['cost'][0][0]) and np.isinf(ref['cost'][0][1]) and np.all(ref['g'][0][1] == 0.0)
+    for form, flags in _ctc_forms():
+        what = 'ctc %s %s %s %s' % ('x'.join(map(str, shape)), family, kind, form)
+        cost, g = _run_ctc(Fq, ref['pred'], labels, il, ll, kind, dev, flags)
+        rc, rg = _check_ctc(cost, g, ref, what)
+        _note('ctc from global cost (%s)' % form, kind, rc)
+        _note('ctc from global gradient (%s)' % form, kind, rg)
+        _note('ctc from global row sums (%s)' % form, kind, _row_sum_check(g, ref['pred'], ref, kind, what))
 
 
 @pytest.mark.gpu
